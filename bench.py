@@ -10,13 +10,18 @@ generated in HBM before the timed region.
 A step = one pass of the hot path over the job (land_trendr_amd/runner.py, the code path the job
 runner uses too): per tile, the index_eqn load kernel (B1 - B2) on the load stream, analyze +
 label, then the tile's label rasters sent point-to-point to rank 0 over RCCL (N > 1), travelling
-while the next tile computes. After the timed steps: the correctness gate (a seeded sample of
-every rank's pixels re-analysed by the CPU oracle and compared with every plane the timed steps
-wrote; any difference fails the run, exit status 3), the load kernel timed alone (its HBM
-roofline) and, unless --e2e-steps 0, end-to-end steps that add H2D of the pinned int16 bands and
-D2H of the label rasters (and, for c5, of every per-year trendline plane) to the same pipeline.
-The oracle (oracle/, test infrastructure) is only the checker and the CPU baseline here: it never
-produces a measured output.
+while the next tile computes.
+
+A plain run sets up, warms up, times the steps, writes its outputs if --dump-outputs DIR is given
+(a seeded sample of rank 0's pixels from every plane the last timed step wrote, DIR/<field>.npy)
+and prints the result line. With --full it goes on after the timed steps: the correctness gate (a
+seeded sample of every rank's pixels re-analysed by the CPU oracle and compared with every plane
+the timed steps wrote; any difference fails the run, exit status 3), the load kernel timed alone
+(its HBM roofline), joined steps, the N > 1 tiling at N = 1, the CPU baseline and, unless
+--e2e-steps 0, end-to-end steps that add H2D of the pinned int16 bands and D2H of the label
+rasters (and, for c5, of every per-year trendline plane) to the same pipeline. The oracle
+(oracle/, test infrastructure) is only the checker and the CPU baseline here: it never produces a
+measured output.
 """
 import argparse
 import json
@@ -236,6 +241,41 @@ def parity_sample(runner, params, n_sample, threads, seed=12345):
     return checked, bad, per_field
 
 
+DUMP_BYTES = 48 << 20   # all files of one --dump-outputs together stay under this
+DUMP_PIXELS = 1 << 18   # and hold at most this many pixels
+
+
+def dump_outputs(runner, out_dir, seed=2468):
+    """--dump-outputs: what the last step left in this rank's output planes (runner.outs, the
+    arrays a caller of runner.step reads) for a fixed, seeded sample of its pixels, one
+    <field>.npy per field in binary64 (every plane's type converts exactly): [n] for a per-pixel
+    field, [rows, n] for a per-rule or per-year one, the sampled pixels in tile order. The sample
+    depends on the tiling and the fields only, so two builds run with the same arguments write
+    the same pixels. Returns {field: shape}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    sizes = np.array([it.tile.n for it in runner.items], np.int64)
+    total = int(sizes.sum())
+    if total == 0:
+        return {}
+    rows = sum(1 if x.ndim == 1 else x.shape[0] for x in runner.outs[0].values())
+    n = min(total, DUMP_PIXELS, DUMP_BYTES // (8 * rows))
+    flat = np.sort(np.random.default_rng(seed).choice(total, n, replace=False))
+    starts = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+    tile_of = np.searchsorted(starts, flat, side='right') - 1
+    parts = {f: [] for f in runner.outs[0]}
+    for k in np.unique(tile_of):
+        cols = torch.from_numpy(flat[tile_of == k] - starts[k]).to(runner.eng.device)
+        for f, plane in runner.outs[k].items():
+            parts[f].append(plane[..., cols].double().cpu().numpy())
+    shapes = {}
+    for f, p in parts.items():
+        a = np.concatenate(p, axis=-1)
+        np.save(os.path.join(out_dir, f + '.npy'), a)
+        shapes[f] = list(a.shape)
+    return shapes
+
+
 def _pinned_like(t):
     """A pinned, compact host copy of the [K, NB, n] bands t in t's layout: planar, or
     pixel-interleaved (a [K, n, NB] buffer viewed as [K, NB, n])."""
@@ -332,6 +372,14 @@ def main():
     ap.add_argument('--steps', type=int, default=3)
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--config', default='c2', choices=sorted(CONFIGS))
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run the correctness gate against the oracle, '
+                         'the load kernel alone, joined steps, end-to-end steps, the N > 1 tiling '
+                         'and the CPU baseline (the options below that shape them apply only '
+                         'with --full)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write a seeded sample of rank 0\'s pixels from '
+                         'every output plane of the last timed step to DIR/<field>.npy (binary64)')
     ap.add_argument('--pixels', type=int, default=0, help='pixels per scene (default: config)')
     ap.add_argument('--tile', type=int, default=0,
                     help='pixels per tile (0: the whole scene for a labels-only config on one '
@@ -467,13 +515,18 @@ def main():
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     elapsed = float(elapsed.item())
     index_ms = runner.index_ms()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(runner, args.dump_outputs)
 
     # correctness gate on this run's own outputs: no pixel may be flagged as an unemulated path,
     # and a seeded sample of the pixels must match the oracle in every plane the steps wrote
-    n_numeric = sum(int(((o['status'][:it.tile.n] & 16) != 0).sum().item())
-                    for o, it in zip(runner.outs, items))
+    n_numeric = None
+    if args.full:
+        n_numeric = sum(int(((o['status'][:it.tile.n] & 16) != 0).sum().item())
+                        for o, it in zip(runner.outs, items))
     psample = None
-    if args.parity_sample > 0:
+    if args.full and args.parity_sample > 0:
         avail, quota = host_cores()
         thr = avail if quota is None else max(1, min(avail, int(math.ceil(quota))))
         t_ps = time.perf_counter()
@@ -490,7 +543,7 @@ def main():
     # the exchange (N > 1): every label tile the writer received equals the owner's copy,
     # compared as per-(tile, field) position-weighted byte sums all-reduced to every rank
     xcheck = None
-    if gather:
+    if args.full and gather:
         ex = runner.exchange
         own = ex.checksums(mosaic.mine)
         tot = own.to(dev)
@@ -504,16 +557,24 @@ def main():
                                'received label planes vs the owners\' (all-reduced)'}
     # the load kernel alone (its HBM roofline): one tile, serially, after the timed region
     it0 = items[0]
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    eng.index_tile(index_fn, it0.bands, out=it0.values)
-    ev[0].record()
-    for _ in range(5):
+    index_alone = None
+    if args.full:
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
         eng.index_tile(index_fn, it0.bands, out=it0.values)
-    ev[1].record()
-    torch.cuda.synchronize()
-    index_alone_ms = ev[0].elapsed_time(ev[1]) / 5
-    K0 = it0.scene.n_obs
-    index_bytes = K0 * it0.tile.n * 6  # two int16 band planes read, one int16 plane written
+        ev[0].record()
+        for _ in range(5):
+            eng.index_tile(index_fn, it0.bands, out=it0.values)
+        ev[1].record()
+        torch.cuda.synchronize()
+        index_alone_ms = ev[0].elapsed_time(ev[1]) / 5
+        K0 = it0.scene.n_obs
+        index_bytes = K0 * it0.tile.n * 6  # two int16 band planes read, one int16 plane written
+        index_alone = {'ms': round(index_alone_ms, 4), 'pixels': it0.tile.n,
+                       'bytes': index_bytes,
+                       'achieved': round(index_bytes / (index_alone_ms * 1e-3) / 1e9, 1),
+                       'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                       'frac': round(index_bytes / (index_alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                     4)}
 
     # the dominant kernel with no previous step's resolve beside it: in the pipelined timed steps
     # each analyze launch shares the CUs with the previous step's resolve for part of its time
@@ -523,7 +584,7 @@ def main():
     # the job runner's per-tile ring (job.py) runs joined steps
     kern_ms_joined = None
     joined = None
-    if not args.no_overlap:
+    if args.full and not args.no_overlap:
         eng.set_timing(True)
         eng.stage_ms()  # reset
         n_joined = 2
@@ -549,7 +610,7 @@ def main():
                           '(runner.step overlap, safe for changing inputs)'}
 
     e2e = None
-    if args.e2e_steps > 0:
+    if args.full and args.e2e_steps > 0:
         if dist is not None:
             dist.barrier()
         e2e_runner, e2e_tile = runner, mosaic.tile
@@ -602,7 +663,8 @@ def main():
     # per-tile completion events as the label exchange uses them), so the driver's N = 1 point and
     # its N > 1 points can be compared pipeline for pipeline
     tiled = None
-    if world == 1 and not mosaic_cfg and mosaic.tile > (1 << 24) and args.tiled_steps > 0:
+    if (args.full and world == 1 and not mosaic_cfg and mosaic.tile > (1 << 24)
+            and args.tiled_steps > 0):
         m3 = Mosaic([P], 1 << 24, 1, 0, 'by_scene')
         items3 = mosaic_inputs(m3, cfg['years'], cfg['k'][0], cfg['k'][1], cfg['mask'],
                                cfg['seed'], dev, TARGET,
@@ -674,6 +736,7 @@ def main():
         'metric': 'Mpixels/sec full analyze (%d-yr series)' % cfg['years'],
         'value': round(value, 4), 'unit': 'Mpixels/s', 'n_gpus': world, 'steps': args.steps,
         'warmup': args.warmup, 'ms_per_step': round(elapsed / args.steps * 1e3, 3),
+        'full': args.full, 'dumped_outputs': dumped,
         'higher_is_better': True, 'scaling': 'strong' if mosaic_cfg else 'weak',
         'vs_baseline': None, 'dtype': 'f64',
         'data': 'synthetic (SURVEY.md 8(d) generator, seeded per scene, generated in HBM)',
@@ -754,12 +817,7 @@ def main():
                        'lt_index_kernel4 (hiprtc, index_eqn "%s", int16 bands -> int16)'
                        % args.index_eqn),
             'ms_per_launch_overlapped': r(index_ms, 3),
-            'alone': {'ms': round(index_alone_ms, 4), 'pixels': it0.tile.n,
-                      'bytes': index_bytes,
-                      'achieved': round(index_bytes / (index_alone_ms * 1e-3) / 1e9, 1),
-                      'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                      'frac': round(index_bytes / (index_alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                    4)}},
+            'alone': index_alone},
         'expand_stage': {'ms_per_launch': round(stages.get('expand', 0.0) / n_launch, 3),
                          'kernel': 'trendline_expand_kernel (per-year planes from the compact '
                                    'trendline, on its own stream beside the next analyze)'}
@@ -772,7 +830,7 @@ def main():
         'n_gt_1_tiling': None if tiled is None else dict(
             tiled, ratio_to_value=round(tiled['value'] / value, 4)),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         res['cpu_baseline'] = cpu_baseline(cfg, args.cpu_seconds)
     if rank == 0:
         print(json.dumps(res), flush=True)

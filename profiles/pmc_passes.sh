@@ -13,7 +13,7 @@ python3 -c "import sys; sys.path.insert(0, '$R'); from land_trendr_amd._abi impo
 run() {
   name=$1; shift
   timeout -s KILL 240 rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -o run -- \
-    python3 $R/bench.py $ARGS --no-cpu-baseline > $OUT/$name.log 2>&1
+    python3 $R/bench.py --full $ARGS --no-cpu-baseline > $OUT/$name.log 2>&1
   echo "pass $name ok"
 }
 run sq1 SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE GRBM_COUNT

@@ -53,6 +53,45 @@ def test_valu_peak_is_the_measured_mix_rate():
     assert 4.0 < cyc['mix_c2'] < 4.6 and 2.0 < cyc['add_u32'] < 2.6
 
 
+def test_dump_outputs_writes_a_fixed_seeded_sample(tmp_path, monkeypatch):
+    """bench.dump_outputs: one binary64 <field>.npy per output plane, the same seeded pixels of
+    the tiles' valid parts on every call, and all files together within DUMP_BYTES."""
+    import types
+
+    import numpy as np
+    import torch
+
+    sizes, W, R = (50, 37), 64, 3  # two tiles of a 64-px slab, the second one short
+    outs = [{'status': torch.arange(W, dtype=torch.int32) + 1000 * k,
+             'matched': (torch.arange(R * W).reshape(R, W) % 2).to(torch.uint8),
+             'magnitude': torch.arange(R * W, dtype=torch.float64).reshape(R, W) / 3 + k}
+            for k in range(2)]
+    runner = types.SimpleNamespace(
+        items=[types.SimpleNamespace(tile=types.SimpleNamespace(n=n)) for n in sizes],
+        outs=outs, eng=types.SimpleNamespace(device='cpu'))
+    shapes = bench.dump_outputs(runner, str(tmp_path / 'a'))
+    assert shapes == {'status': [87], 'matched': [R, 87], 'magnitude': [R, 87]}  # every pixel
+    a = {f: np.load(tmp_path / 'a' / (f + '.npy')) for f in shapes}
+    assert all(x.dtype == np.float64 for x in a.values())
+    cols = [np.arange(n) for n in sizes]
+    for f in shapes:
+        want = np.concatenate([outs[k][f][..., cols[k]].double().numpy() for k in range(2)], -1)
+        assert np.array_equal(a[f], want), f
+    # a budget smaller than the tiles: a strict sample, identical from call to call
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 8 * 7 * 20)  # 7 rows in all -> 20 pixels
+    s1 = bench.dump_outputs(runner, str(tmp_path / 'b'))
+    s2 = bench.dump_outputs(runner, str(tmp_path / 'c'))
+    assert s1 == s2 == {'status': [20], 'matched': [R, 20], 'magnitude': [R, 20]}
+    total = 0
+    for f in s1:
+        b, c = (np.load(tmp_path / d / (f + '.npy')) for d in 'bc')
+        assert np.array_equal(b, c), f
+        total += b.nbytes
+    assert total <= 8 * 7 * 20
+    st = np.load(tmp_path / 'b' / 'status.npy')  # never a pixel of a slab's unused tail
+    assert ((st % 1000) < np.where(st >= 1000, sizes[1], sizes[0])).all()
+
+
 def test_despike_step_as_four_compares():
     def reference(d1, d2, k):
         mono = (d1 >= 0 and d2 >= 0) or (d1 <= 0 and d2 <= 0)

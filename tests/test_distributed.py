@@ -290,9 +290,9 @@ def _own_worker(rank, world, port, scene_px, tile, assign, result_path):
 ])
 @pytest.mark.timeout(180)
 def test_own_label_planes_per_rank_match_single_process(tmp_path, world, px, tile, assign):
-    """The end-to-end 'own' label mode at N > 1 (bench.py --e2e-labels own): no
-    rank sends anything; the ranks' per-tile label planes, laid side by side by mosaic position,
-    are the single-process rasters."""
+    """The end-to-end 'own' label mode at N > 1 (bench.py --full --e2e-labels own):
+    no rank sends anything; the ranks' per-tile label planes, laid side by side by mosaic
+    position, are the single-process rasters."""
     path = str(tmp_path / 'own')
     mp.spawn(_own_worker, args=(world, _free_port(), px, tile, assign, path), nprocs=world,
              join=True)

@@ -23,7 +23,7 @@ def main():
     rows = [{'kernel': k, 'grid_x': g, 'launches': len(v), 'avg_ms': round(sum(v) / len(v), 3),
              'min_ms': round(min(v), 3), 'max_ms': round(max(v), 3)}
             for (k, g), v in sorted(groups.items())]
-    res = {'command': 'rocprofv3 --kernel-trace --stats -- python3 bench.py (default: c2, timed '
+    res = {'command': 'rocprofv3 --kernel-trace --stats -- python3 bench.py --full (c2, timed '
                       'steps of one 49 Mpx launch + warmup, then the end-to-end and N>1-tiling '
                       'legs with 16.8 Mpx tiles)',
            'by_launch': rows,
