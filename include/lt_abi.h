@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define LT_ABI_VERSION 7
+#define LT_ABI_VERSION 8
 #define LT_MAX_YEARS 64   /* distinct calendar years per scene (T <= 40 in every config) */
 #define LT_MAX_OBS 1024   /* observations per scene (K*T) */
 #define LT_MAX_RULES 16
@@ -331,6 +331,34 @@ int lt_raster_assemble(lt_ctx* ctx, const lt_raster_job* jobs, int n_jobs, void*
  * set iff winner[y * stride + p] == o for some y < n_years, p < n_pix. Asynchronous on `stream`. */
 int lt_winner_presence(lt_ctx* ctx, const int16_t* winner, int64_t stride, int32_t n_years,
                        int64_t n_pix, int32_t n_obs, uint32_t* bits, void* stream);
+
+/* ---- ingest: TIFF strips decoded on the device (ABI 8) -------------------------------------------
+ * One strip-organised TIFF image whose compressed strips are in device memory: the arguments of
+ * lt_tiff_decode_strips (include/lt_io.h), every pointer a DEVICE pointer. */
+typedef struct {
+  const uint8_t* file;      /* DEVICE: the bytes that hold every strip (the file, or a slice of it) */
+  int64_t file_size;
+  const uint64_t* offsets;  /* DEVICE [n_strips], relative to `file`                                */
+  const uint64_t* counts;   /* DEVICE [n_strips]                                                    */
+  int64_t n_strips;
+  int32_t compression;      /* 1 or 5                                                               */
+  int32_t predictor;        /* 1 or 2                                                               */
+  int32_t bps;              /* bytes per sample: 1, 2, 4, 8                                         */
+  int32_t big_endian;
+  int64_t width, height;
+  int32_t bands, planar;    /* planar 1 (chunky: de-interleaved here) or 2                          */
+  int64_t rows_per_strip;
+  void* out;                /* DEVICE [bands][height][width], native byte order                     */
+  int32_t* err;             /* DEVICE one word: zeroed by the call, then the LT_IO_ERR_* of some
+                               failing strip (first writer wins, atomicCAS from 0), else 0          */
+} lt_strips_job;
+/* lt_tiff_decode_strips (lt_io.h) for n_jobs images whose compressed strips are in device memory,
+ * asynchronous on `stream`; same results, same zero padding of short strips, same ignored extra
+ * strips. LT_ERR_ARG for what the host function rejects and for strips of 1 MiB or more decoded.
+ * One lane per strip (the LZW core of land_trendr_amd/csrc/lt_lzw_core.h, the source liblt_io.so's
+ * lt_lzw_decode_core is compiled from); the context owns the lanes' string tables (16 KB a lane,
+ * grown on demand). A failing strip's rows are unspecified; every other strip is decoded. */
+int lt_tiff_decode_strips_dev(lt_ctx* ctx, const lt_strips_job* jobs, int n_jobs, void* stream);
 
 /* Stage timing: when enabled, each lt_analyze_tile brackets its kernels with hipEvents on the
  * launch stream; lt_ctx_stage_ms returns the accumulated milliseconds per stage

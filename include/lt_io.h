@@ -23,6 +23,11 @@ int64_t lt_lzw_decode(const uint8_t* in, int64_t n_in, uint8_t* out, int64_t cap
 /* Raw bytes -> one TIFF LZW strip (libtiff's code stream: Clear first, 9..12-bit codes, early
  * change, Clear when the table is full). cap >= n_in * 3 / 2 + 16 always suffices. */
 int64_t lt_lzw_encode(const uint8_t* in, int64_t n_in, uint8_t* out, int64_t cap);
+/* lt_lzw_decode's contract by the decoder core the device runs (land_trendr_amd/csrc/
+ * lt_lzw_core.h, one lane per strip in lt_tiff_decode_strips_dev), compiled for the host: same
+ * counts, bytes and errors; LT_IO_ERR_ARG for cap >= 1 MiB (its table packs 20-bit positions);
+ * no byte of out past the returned count is written. */
+int64_t lt_lzw_decode_core(const uint8_t* in, int64_t n_in, uint8_t* out, int64_t cap);
 
 /* Every strip of one strip-organised TIFF image decoded on `threads` threads into `out`, the
  * [bands, height, width] samples in native byte order (what ds2array gives per band,

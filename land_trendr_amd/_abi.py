@@ -10,7 +10,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'liblt_hip.so')
 
-LT_ABI_VERSION = 7
+LT_ABI_VERSION = 8
 LT_MAX_YEARS = 64
 LT_MAX_OBS = 1024
 LT_MAX_RULES = 16
@@ -146,6 +146,18 @@ class LtRasterJob(ctypes.Structure):
                 ('out_type', ctypes.c_int32), ('fill', ctypes.c_double), ('out', ctypes.c_void_p)]
 
 
+class LtStripsJob(ctypes.Structure):
+    """lt_strips_job: one strip-organised TIFF image whose strips are in device memory."""
+    _fields_ = [('file', ctypes.c_void_p), ('file_size', ctypes.c_int64),
+                ('offsets', ctypes.c_void_p), ('counts', ctypes.c_void_p),
+                ('n_strips', ctypes.c_int64), ('compression', ctypes.c_int32),
+                ('predictor', ctypes.c_int32), ('bps', ctypes.c_int32),
+                ('big_endian', ctypes.c_int32), ('width', ctypes.c_int64),
+                ('height', ctypes.c_int64), ('bands', ctypes.c_int32), ('planar', ctypes.c_int32),
+                ('rows_per_strip', ctypes.c_int64), ('out', ctypes.c_void_p),
+                ('err', ctypes.c_void_p)]
+
+
 class LtIndexIO(ctypes.Structure):
     _fields_ = [('n_pix', ctypes.c_int64), ('n_obs', ctypes.c_int64),
                 ('obs_stride', ctypes.c_int64), ('band_stride', ctypes.c_int64),
@@ -182,7 +194,7 @@ EXPORTS = ['lt_abi_version', 'lt_ctx_create', 'lt_ctx_destroy', 'lt_last_error',
            'lt_ctx_last_deferred', 'lt_index_codegen', 'lt_index_compile', 'lt_index_apply',
            'lt_settings_compile', 'lt_raster_assemble', 'lt_winner_presence',
            'lt_index_linearize', 'lt_ctx_set_jit_mode', 'lt_jit_prepare', 'lt_ctx_jit_stats',
-           'lt_jit_source', 'lt_analyze_tiles_ev']
+           'lt_jit_source', 'lt_analyze_tiles_ev', 'lt_tiff_decode_strips_dev']
 
 LT_JIT_SYNC, LT_JIT_ASYNC = 0, 1
 LT_JIT_SRC_SPEC, LT_JIT_SRC_SCENE, LT_JIT_SRC_FIELDS = 1, 2, 4
@@ -259,6 +271,7 @@ def load_lib(path=None):
                                   ctypes.POINTER(LtIndexProg), ctypes.c_int32, ctypes.c_int32,
                                   ctypes.c_int32, ctypes.c_char_p, ctypes.c_int64]
     lib.lt_jit_source.restype = ctypes.c_int
+    lib.lt_tiff_decode_strips_dev.argtypes = [vp, ctypes.POINTER(LtStripsJob), ctypes.c_int, vp]
     if lib.lt_abi_version() != LT_ABI_VERSION:
         raise RuntimeError('liblt_hip.so ABI %d != %d' % (lib.lt_abi_version(), LT_ABI_VERSION))
     if path is None:

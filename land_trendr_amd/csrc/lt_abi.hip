@@ -304,6 +304,7 @@ struct lt_ctx {
   // analyze kernel drops from 12.3 to 9.0-9.3 ms per 16.8 Mpx tile, but the expand kernel takes
   // 8.1 ms alone (28 GB of rows at 3.5 TB/s) and gets CU slots only between analyze launches
   bool tl_split = false;
+  lt::DecodeScratch dec;  // the strip decoder's scratch (lt_decode.hip)
 };
 
 static int fail(lt_ctx* c, int code, const char* fmt, const char* detail = "") {
@@ -314,6 +315,14 @@ static int fail(lt_ctx* c, int code, const char* fmt, const char* detail = "") {
   }
   return code;
 }
+
+namespace lt {  // the context as lt_decode.hip sees it (lt_launch.h)
+DecodeScratch& ctx_decode(lt_ctx* c) { return c->dec; }
+int ctx_device(const lt_ctx* c) { return c->device; }
+int ctx_fail(lt_ctx* c, int code, const char* fmt, const char* detail) {
+  return fail(c, code, fmt, detail);
+}
+}  // namespace lt
 
 #define HIP_OR_FAIL(ctx, expr)                                       \
   do {                                                               \
@@ -418,6 +427,7 @@ int lt_ctx_destroy(lt_ctx* c) {
   if (c->d_ndefer) (void)hipFree(c->d_ndefer);
   if (c->d_scene) (void)hipFree(c->d_scene);
   if (c->d_xtab) (void)hipFree(c->d_xtab);
+  lt::decode_release(c->dec);
   for (auto& kv : c->index_fns) {
     if (kv.second->mod) (void)hipModuleUnload(kv.second->mod);
     delete kv.second;

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/lt_io.h"
+#include "lt_lzw_core.h"
 
 namespace {
 
@@ -413,6 +414,13 @@ int64_t lt_tiff_encode_strips(const uint8_t* in, int bands, int64_t rows, int64_
     total += m;
   }
   return total;
+}
+
+// The decoder core the device runs (lt_lzw_core.h, lt_decode.hip), compiled for the host: what the
+// CPU tests drive, and the place to look when a device decode misbehaves (the same source).
+int64_t lt_lzw_decode_core(const uint8_t* in, int64_t n_in, uint8_t* out, int64_t cap) {
+  uint32_t table[4096];
+  return lt_lzw::decode(in, n_in, out, cap, lt_lzw::FlatTable{table});
 }
 
 }  // extern "C"

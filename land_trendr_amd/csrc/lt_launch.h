@@ -1,4 +1,5 @@
-// lt_launch.h — what lt_abi.hip hands the analyze-stage dispatch for one tile.
+// lt_launch.h — what lt_abi.hip hands the analyze-stage dispatch for one tile, and what it shares
+// with the strip decoder (lt_decode.hip).
 //
 // The kernels of the analyze and resolve stages (lt_kernels.h) are instantiated in a dispatch
 // translation unit of their own: lt_dispatch.hip in the product library, a profiling unit in the
@@ -28,6 +29,28 @@ struct TileLaunch {
   uint64_t* tl_bits = nullptr;   // the compact trendline ([4][n_pix] words), or null
   double* tl_eqn = nullptr;      // its segment eqns ([Y-1][n_pix] (m, b) pairs)
 };
+
+// The strip decoder's share of a context (lt_decode.hip, lt_tiff_decode_strips_dev): scratch grown
+// on demand, freed with the context (decode_release, called by lt_ctx_destroy). One set per stream
+// the decoder was called on: launches on one stream run one after the other and share a set, while
+// several rasters decode side by side on streams of their own.
+struct DecodeScratch {
+  struct Set {
+    uint32_t* d_tables = nullptr;  // the lanes' LZW string tables: [waves][4096 entries][64 lanes]
+    int64_t table_lanes = 0;
+    uint8_t* d_strips = nullptr;   // chunky images: one decoded strip per lane (de-interleaved
+    int64_t strips_bytes = 0;      // from there)
+  };
+  static constexpr int kMaxSets = 16;
+  hipStream_t stream[kMaxSets] = {};
+  Set set[kMaxSets];
+  int n_sets = 0;
+};
+void decode_release(DecodeScratch& s);
+// What lt_decode.hip needs of a context (defined in lt_abi.hip beside lt_ctx).
+DecodeScratch& ctx_decode(lt_ctx* c);
+int ctx_device(const lt_ctx* c);
+int ctx_fail(lt_ctx* c, int code, const char* fmt, const char* detail);
 
 // Stage 1: the analyze kernel over every pixel of the tile, on l.stream.
 hipError_t launch_analyze(const TileLaunch& l);

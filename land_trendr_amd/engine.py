@@ -4,6 +4,7 @@ One Engine per GPU (per process). torch provides device memory and the stream on
 happens in land_trendr_amd/liblt_hip.so. There is no CPU path.
 """
 import ctypes
+import threading
 
 import torch
 
@@ -44,6 +45,7 @@ class Engine:
         if rc != 0:
             raise LtError('lt_ctx_create failed (%d)' % rc)
         self.ctx = ctx
+        self._decode_lock = threading.Lock()
 
     def close(self):
         if self.ctx:
@@ -286,6 +288,69 @@ class Engine:
         self._check(self.lib.lt_raster_assemble(self.ctx, arr, len(jobs),
                                                 ctypes.c_void_p(st.cuda_stream)),
                     'lt_raster_assemble')
+
+    # --- ingest: TIFF strips decoded on the device (lt_tiff_decode_strips_dev, lt_decode.hip) ---
+    def decode_strips(self, jobs, stream=None):
+        """Every strip of len(jobs) strip-organised TIFF images whose compressed bytes are in
+        device memory, decoded by the HIP strip decoder in one call. A job is a dict:
+          file      uint8 device tensor: the bytes that hold every strip (the file or a slice);
+          offsets, counts  int64 (or uint64) device tensors [n_strips], offsets relative to file;
+          compression (1 or 5), predictor (1 or 2), planar (1 or 2), rows_per_strip;
+          dtype     the numpy sample type as stored (its byte order is the file's);
+          width, height, bands;
+          out       optional contiguous [bands, height, width] device tensor to fill.
+        Returns (the list of [bands, height, width] tensors, native byte order; the int32 error
+        words, one per job: 0, or the LT_IO_ERR_* of a failing strip once the stream has run).
+        Asynchronous on `stream`; the caller keeps the input tensors alive until it has run."""
+        import numpy as np
+        n = len(jobs)
+        arr = (_abi.LtStripsJob * max(n, 1))()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(st):  # (tensors made here belong to the stream that fills them)
+            err = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)  # zeroed by the call
+            made = [torch.empty((int(j['bands']), int(j['height']), int(j['width'])),
+                                dtype=torch.from_numpy(
+                                    np.empty(0, np.dtype(j['dtype']).newbyteorder('='))).dtype,
+                                device=self.device) if j.get('out') is None else None
+                    for j in jobs]
+        outs = []
+        for k, j in enumerate(jobs):
+            dt = np.dtype(j['dtype'])
+            tdt = torch.from_numpy(np.empty(0, dt.newbyteorder('='))).dtype
+            shape = (int(j['bands']), int(j['height']), int(j['width']))
+            out = j.get('out') if j.get('out') is not None else made[k]
+            if (tuple(out.shape) != shape or out.dtype != tdt or out.device != self.device or
+                    not out.is_contiguous()):
+                raise LtError('decode_strips: out must be a contiguous %s %s tensor on %s'
+                              % (tdt, shape, self.device))
+            f, offs, cnts = j['file'], j['offsets'], j['counts']
+            if (f.dtype != torch.uint8 or f.dim() != 1 or not f.is_contiguous() or
+                    f.device != self.device):
+                raise LtError('decode_strips: file must be a contiguous uint8 tensor on %s'
+                              % self.device)
+            for t in (offs, cnts):
+                if (t.dtype not in (torch.int64, torch.uint64) or t.dim() != 1 or
+                        not t.is_contiguous() or t.device != self.device or
+                        t.shape != offs.shape):
+                    raise LtError('decode_strips: offsets / counts must be contiguous 64-bit '
+                                  '[n_strips] tensors on %s' % self.device)
+            a = arr[k]
+            a.file, a.file_size = f.data_ptr(), f.numel()
+            a.offsets, a.counts, a.n_strips = offs.data_ptr(), cnts.data_ptr(), offs.numel()
+            a.compression, a.predictor = int(j['compression']), int(j['predictor'])
+            a.bps = dt.itemsize
+            a.big_endian = 1 if (dt.byteorder == '>' or
+                                 (dt.byteorder == '=' and np.little_endian is False)) else 0
+            a.width, a.height, a.bands = shape[2], shape[1], shape[0]
+            a.planar, a.rows_per_strip = int(j['planar']), int(j['rows_per_strip'])
+            a.out = out.data_ptr()
+            a.err = err.data_ptr() + 4 * k
+            outs.append(out)
+        with self._decode_lock:  # one context: one caller at a time (ingest decodes on threads)
+            self._check(self.lib.lt_tiff_decode_strips_dev(self.ctx, arr, n,
+                                                           ctypes.c_void_p(st.cuda_stream)),
+                        'lt_tiff_decode_strips_dev')
+        return outs, err[:n]
 
     # --- JIT kernels of tiles carrying a program (lt_jit.h; lt_ctx_set_jit_mode, lt_jit_prepare) ---
     def set_jit_mode(self, asynchronous):

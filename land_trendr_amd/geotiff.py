@@ -201,6 +201,88 @@ class GeoTiff:
         return np.ascontiguousarray(a).astype(self.dtype.newbyteorder('='), copy=False)
 
 
+    def device_eligible(self):
+        """Whether read_device takes this file: strip-organised, uncompressed or LZW, predictor 1
+        (or 2 with integer samples), 8/16/32/64-bit samples, strips that decode to less than
+        1 MiB (the device decoder's table packs 20-bit positions, lt_lzw_core.h)."""
+        t = self.tags
+        if 273 not in t or 279 not in t or self.compression not in (1, 5):
+            return False
+        if not (self.predictor == 1 or (self.predictor == 2 and self.dtype.kind in 'iu')):
+            return False
+        if self.bits not in (8, 16, 32, 64) or self.planar not in (1, 2):
+            return False
+        if self.width <= 0 or self.height <= 0 or self.bands <= 0:
+            return False
+        rps = min(int(t.get(278, (self.height,))[0]), self.height)
+        spp = self.bands if self.planar == 1 else 1
+        return 0 < rps and rps * self.width * spp * self.dtype.itemsize < (1 << 20)
+
+    def read_device(self, engine, out=None, stream=None, check=True, staging=None):
+        """read() on the GPU: the byte range that spans the strips is copied from the mapping into
+        a pinned staging buffer (`staging`: a pinned uint8 tensor to reuse when it is large
+        enough), sent to the device with the strips' offsets and counts, and decoded there by
+        engine.decode_strips into `out` (a contiguous [bands, rows, cols] device tensor of the
+        sample type; made when None), asynchronously on `stream`. check=True: the stream is
+        synchronised and a failing strip raises TiffError, as read() raises; check=False: the
+        caller reads the returned error word (int32 device tensor, 0 = no error) once the stream
+        has run, and leaves `staging` alone until the event self.staged (recorded behind the copy
+        to the device) has completed. A file that is not device_eligible()
+        raises TiffError and nothing is decoded. Returns (out, error word)."""
+        if not self.device_eligible():
+            raise TiffError('not eligible for the device decoder (GeoTiff.device_eligible)')
+        import torch
+        from .engine import LtError
+        t = self.tags
+        H, B = self.height, self.bands
+        rps = min(int(t.get(278, (H,))[0]), H)
+        per_band = -(-H // rps)
+        need = per_band if self.planar == 1 else per_band * B
+        offs = np.asarray(t[273], np.int64)
+        cnts = np.asarray(t[279], np.int64)
+        if len(offs) < need or len(cnts) != len(offs):
+            raise TiffError('TIFF strips: fewer strips than the image has')
+        size = len(self._d)
+        # the bytes sent: from the first to the last strip that lies inside the file (a strip
+        # that does not keeps its offset, now outside the slice: the decoder reports it)
+        inside = (offs[:need] >= 0) & (cnts[:need] >= 0) & (offs[:need] + cnts[:need] <= size)
+        lo = int(offs[:need][inside].min()) if inside.any() else 0
+        hi = int((offs[:need] + cnts[:need])[inside].max()) if inside.any() else 0
+        n = hi - lo
+        dev = engine.device
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        m = 2 * len(offs)
+        if staging is None or staging.numel() < n + 8 * m + 8:
+            staging = torch.empty(n + 8 * m + 8, dtype=torch.uint8, pin_memory=True)
+        sv = staging.numpy()
+        sv[:n] = np.frombuffer(self._d, np.uint8, n, lo)
+        n8 = -(-n // 8) * 8  # the offset / count tables behind the bytes, 8-byte aligned
+        tab = sv[n8:n8 + 8 * m].view(np.int64)
+        tab[:len(offs)] = offs - lo
+        tab[len(offs):] = cnts
+        try:
+            with torch.cuda.stream(st):
+                d = torch.empty(n8 + 8 * m, dtype=torch.uint8, device=dev)
+                d.copy_(staging[:n8 + 8 * m], non_blocking=True)
+                # recorded once the bytes have left `staging`: a caller reusing it waits here
+                self.staged = torch.cuda.Event()
+                self.staged.record(st)
+                dt = d[n8:].view(torch.int64)
+                outs, err = engine.decode_strips([dict(
+                    file=d[:n] if n else d[:0], offsets=dt[:len(offs)], counts=dt[len(offs):],
+                    compression=self.compression, predictor=self.predictor, dtype=self.dtype,
+                    width=self.width, height=H, bands=B, planar=self.planar, rows_per_strip=rps,
+                    out=out)], stream=st)
+        except LtError as e:
+            raise TiffError(str(e))
+        if check:
+            st.synchronize()
+            rc = int(err.item())
+            if rc != 0:
+                raise TiffError('TIFF strips: corrupt or unsupported data (%d)' % rc)
+        return outs[0], err
+
+
 def read_bands(path):
     """[bands, rows, cols] numpy array of a GeoTIFF (GDAL's ReadAsArray per band, stacked)."""
     return GeoTiff(path).read()

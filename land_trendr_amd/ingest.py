@@ -293,7 +293,7 @@ class _Offsets:
 
 
 def ingest_stack(rast_fns, grid, mask_fns=None, bands=None, threads=None, pixels=None,
-                 raster_grid=None, on_raster=None):
+                 raster_grid=None, on_raster=None, device_decode=None):
     """parse_mapper over every analysis raster, as planes for analysis_reducer_batch.
 
     rast_fns: the (decompressed) analysis rasters, in the mapper order that becomes each pixel's
@@ -311,7 +311,13 @@ def ingest_stack(rast_fns, grid, mask_fns=None, bands=None, threads=None, pixels
     raster_grid: (geotransform, rows, cols) when grid point p is pixel p of such a raster (the
     job's raster order): rasters of that georeferencing are read by slicing, not by offsets.
     on_raster(k, bands_k [nb, Q], valid_k [Q]): called on the worker thread once raster k's planes
-    are complete (the job copies them to the GPU while the other rasters decode)."""
+    are complete (the job copies them to the GPU while the other rasters decode).
+    device_decode(k, ds) -> bool: offered raster k (its open GeoTiff) when its planes are the
+    stack's as they are (raster order, every band, the whole grid gathered: one full range, or a
+    job's tiles back to back; what the host decodes in place); True: the callee has decoded it — into plane
+    k of a device stack of its own (LocalJob decode='device') — so bands[k] is left unwritten here
+    and on_raster gets None for bands_k; False: the host path, as without it. Masks are decoded
+    on the host either way."""
     from concurrent.futures import ThreadPoolExecutor
     lng, lat = grid if isinstance(grid, tuple) else grid_points(grid)
     P = len(lng)
@@ -343,6 +349,10 @@ def ingest_stack(rast_fns, grid, mask_fns=None, bands=None, threads=None, pixels
     offsets = _Offsets(lng, lat, raster_grid)
     sel = [b - 1 for b in numbers]
     spans = [(p0, p1, q0) for p0, p1, q0 in ranges]
+    # the ranges are the whole grid in order (a one-rank job's tiles, back to back): column q of
+    # the gathered arrays is grid point q, so a raster-order raster's planes are its own pixels
+    full_range = (bool(ranges) and ranges[0][0] == 0 and ranges[-1][1] == P and
+                  all(a[1] == b[0] for a, b in zip(ranges, ranges[1:])))
 
     def take(flat, idx, ok, ident, out):
         """Samples of the gathered grid points from a raster's flat [..., H*W] samples."""
@@ -359,6 +369,7 @@ def ingest_stack(rast_fns, grid, mask_fns=None, bands=None, threads=None, pixels
 
     def one(k):
         fn = rast_fns[k]
+        on_device = False
         ds = first if k == 0 else _open(fn)
         if ds.dtype.newbyteorder('=') != dtype:
             raise ValueError('%s: sample type %s differs from the stack\'s %s' % (fn, ds.dtype, dtype))
@@ -366,8 +377,11 @@ def ingest_stack(rast_fns, grid, mask_fns=None, bands=None, threads=None, pixels
             raise Exception('Band %s requested but raster only has %s bands' % (max(numbers),
                                                                                  ds.bands))
         idx, ok, ident = offsets(ds)
-        if (ident and idx is None and sel == list(range(ds.bands)) and len(spans) == 1 and
-                spans[0][:2] == (0, P) and ds.width * ds.height == P):
+        whole = (ident and idx is None and sel == list(range(ds.bands)) and
+                 ds.width * ds.height == P)  # raster order, every band
+        if whole and full_range and device_decode is not None and device_decode(k, ds):
+            on_device = True  # decoded by the callee into its own (device) plane k
+        elif whole and len(spans) == 1 and spans[0][:2] == (0, P):
             # raster order, every band, one full range: decoded in place (no copy of the planes)
             ds.read(threads=per_file, out=out_bands[k].reshape(ds.bands, ds.height, ds.width))
         else:
@@ -387,7 +401,7 @@ def ingest_stack(rast_fns, grid, mask_fns=None, bands=None, threads=None, pixels
             drop = (mval == 0) if mok is None else (mok & (mval == 0))
             v &= ~drop
         if on_raster is not None:
-            on_raster(k, out_bands[k], valid[k])
+            on_raster(k, None if on_device else out_bands[k], valid[k])
         return filename2date(fn)
 
     total = threads or host_threads()

@@ -49,14 +49,60 @@ OUT_GRID = '%s/output/pix_grid.csv'
 OUT_RASTS = '%s/output/rasters/'
 
 
+class _LazyBands(dict):
+    """An ingest_stack result whose 'bands' array is completed on first access (LocalJob
+    decode='device': the planes of the rasters decoded on the GPU come down from the device
+    stack then; the job itself never asks)."""
+
+    def __init__(self, stack, fill):
+        super().__init__(stack)
+        self._fill = fill
+
+    def _complete(self):
+        fill, self._fill = self._fill, None
+        if fill is not None:
+            fill(dict.__getitem__(self, 'bands'))
+
+    def __getitem__(self, key):
+        if key == 'bands':
+            self._complete()
+        return dict.__getitem__(self, key)
+
+    def get(self, key, default=None):
+        if key == 'bands':
+            self._complete()
+        return dict.get(self, key, default)
+
+    def items(self):
+        self._complete()
+        return dict.items(self)
+
+    def values(self):
+        self._complete()
+        return dict.values(self)
+
+
 class LocalJob:
     def __init__(self, root, job, device=None, tile_pixels=1 << 22, trendline=True,
                  raster_mode='reference', pre_threshold_mode='reference', on_error='raise',
-                 work_dir=None, engine=None):
+                 work_dir=None, engine=None, decode=None):
         """engine: the analysis engine (default: engine.get_engine of `device`, the HIP library);
-        tests pass a CPU double (tests/engine_double.py) to run the multi-rank path over gloo."""
+        tests pass a CPU double (tests/engine_double.py) to run the multi-rank path over gloo.
+        decode: 'host' (default; LT_JOB_DECODE overrides the default) — every raster's strips are
+        decoded by liblt_io.so on the host threads; 'device' — parse() builds the device stack up
+        front and the rasters the HIP strip decoder takes (GeoTiff.device_eligible, read in
+        place: raster order, every band) are decoded on the GPU straight into it, the others on
+        the host as before; decode_stats counts both."""
         if on_error not in ('raise', 'skip'):
             raise ValueError('on_error must be "raise" or "skip"')
+        decode = decode or os.environ.get('LT_JOB_DECODE') or 'host'
+        if decode not in ('host', 'device'):
+            raise ValueError('decode must be "host" or "device"')
+        self.decode = decode
+        self.decode_stats = {'device': 0, 'host': 0}  # rasters by the path that decoded them
+        self.decode_times = {}  # device mode: thread-seconds of parse() inside the decoder
+        self._stack_meta = None  # device mode: (sample type, [K, nb, Q]) of the device stack
+        self._dev_keep = None    # device mode: the device stack behind stack['bands']
         self.root, self.job, self.device = root, job, device
         self.tile_pixels = int(tile_pixels)
         self.trendline = trendline
@@ -216,16 +262,113 @@ class LocalJob:
         # are decoded, on the worker that decoded them, while the other rasters decode: analyze()
         # then starts from the device stack
         self._dev_stack = None
-        up = self._stack_uploader(len(self.rast_fns), len(eqn_bands),
-                                  sum(t.n for t in self.mosaic.mine))
+        self._stack_meta = self._dev_keep = None
+        self.decode_times = {}
+        K, Q = len(self.rast_fns), sum(t.n for t in self.mosaic.mine)
+        up = self._stack_uploader(K, len(eqn_bands), Q)
+        dec = self._device_decoder(up, K, len(eqn_bands), Q) if self.decode == 'device' else None
         self.stack = ingest_stack(self.rast_fns, self.grid_xy, self.mask_fns, bands=eqn_bands,
                                   pixels=[(t.p0, t.p1) for t in self.mosaic.mine],
-                                  raster_grid=self.raster_grid, on_raster=up)
+                                  raster_grid=self.raster_grid, on_raster=up,
+                                  device_decode=dec)
+        t_sync = time.perf_counter()
         if up is not None and up.bands is not None:
             import torch
             torch.cuda.synchronize(up.device)
             self._dev_stack = (up.bands, up.valid)
+        if dec is not None:  # where a device-decode parse spent its time (thread-seconds)
+            self.decode_times = dict(dec.times, sync=time.perf_counter() - t_sync)
+        self.decode_stats = {'device': len(dec.taken) if dec is not None else 0,
+                             'host': K - (len(dec.taken) if dec is not None else 0)}
+        if dec is not None:
+            dec.check()
+            if dec.taken:
+                # the job reads the device stack from here on; stack['bands'] stays usable for
+                # callers: the rasters decoded on the device come down on first access
+                self._stack_meta = (self.stack['bands'].dtype, tuple(self.stack['bands'].shape))
+                self._dev_keep = up.bands
+                self.stack = _LazyBands(self.stack, self._fill_bands(sorted(dec.taken)))
         return self.stack
+
+    def _fill_bands(self, taken):
+        def fill(host):
+            dev, self._dev_keep = self._dev_keep, None
+            for k in taken:
+                host[k] = dev[k].cpu().numpy()
+        return fill
+
+    def _device_decoder(self, up, K, nb, Q):
+        """ingest_stack's device_decode of a decode='device' job (None: host decode for the whole
+        job — no GPU uploader, or a stack above the 64 GB rule analyze() applies for the whole-stack
+        upload). Makes the [K, nb, Q] device stack up front in the first raster's sample type;
+        each accepted raster is staged in a pinned buffer of the calling worker thread and decoded
+        on one of a few streams (GeoTiff.read_device, check=False: check() reads every error
+        word once parse has synchronised)."""
+        import threading
+        import torch
+        if up is None:
+            return None
+        first = GeoTiff(self.rast_fns[0])
+        dtype = first.dtype.newbyteorder('=')
+        if K * nb * Q * dtype.itemsize + K * Q > (64 << 30):
+            return None
+        if self.engine is None:
+            from .engine import get_engine
+            self.engine = get_engine(up.device)
+        eng = self.engine
+        with torch.cuda.device(up.device):
+            up.bands = torch.empty((K, nb, Q), dtype=torch.from_numpy(np.empty(0, dtype)).dtype,
+                                   device=up.device)
+            up.valid = torch.empty((K, Q), dtype=torch.uint8, device=up.device)
+            streams = [torch.cuda.Stream(device=up.device) for _ in range(8)]
+        tl = threading.local()
+        lock = threading.Lock()
+        rast_fns = self.rast_fns
+
+        class Dec:
+            def __init__(self):
+                self.taken, self.errs, self.threads = set(), [], 0
+                # seconds summed over the worker threads: waiting for the staging buffer,
+                # allocating it, and GeoTiff.read_device (staging copy, H2D and launch calls)
+                self.times = {'wait': 0.0, 'alloc': 0.0, 'read': 0.0}
+
+            def __call__(self, k, ds):
+                if (not ds.device_eligible() or ds.bands != nb or
+                        ds.dtype.newbyteorder('=') != dtype or ds.width * ds.height != Q):
+                    return False
+                if not hasattr(tl, 'stream'):
+                    with lock:
+                        tl.stream = streams[self.threads % len(streams)]
+                        self.threads += 1
+                    tl.staging, tl.staged = None, None
+                need = len(ds._d) + 16 * len(ds.tags[273]) + 16
+                t0 = time.perf_counter()
+                if tl.staged is not None:  # the previous raster's bytes have left the buffer
+                    tl.staged.synchronize()
+                t1 = time.perf_counter()
+                if tl.staging is None or tl.staging.numel() < need:
+                    tl.staging = torch.empty(need, dtype=torch.uint8, pin_memory=True)
+                t2 = time.perf_counter()
+                out = up.bands[k].view(ds.bands, ds.height, ds.width)
+                _, err = ds.read_device(eng, out=out, stream=tl.stream, check=False,
+                                        staging=tl.staging)
+                t3 = time.perf_counter()
+                tl.staged = ds.staged
+                with lock:
+                    self.taken.add(k)
+                    self.errs.append((k, err))
+                    for key, dt in (('wait', t1 - t0), ('alloc', t2 - t1), ('read', t3 - t2)):
+                        self.times[key] += dt
+                return True
+
+            def check(self):
+                from .geotiff import TiffError
+                for k, err in sorted(self.errs, key=lambda e: e[0]):
+                    rc = int(err.item())
+                    if rc != 0:
+                        raise TiffError('%s: TIFF strips: corrupt or unsupported data (%d)'
+                                        % (rast_fns[k], rc))
+        return Dec()
 
     def _stack_uploader(self, K, nb, Q):
         """The per-raster H2D of parse() (None when the job does not run on a GPU, or
@@ -251,7 +394,8 @@ class LocalJob:
                                                  device=dev)
                         self.valid = torch.empty((K, Q), dtype=torch.uint8, device=dev)
                 with torch.cuda.device(dev):
-                    self.bands[k].copy_(torch.from_numpy(b))
+                    if b is not None:  # (None: decoded on the device, already in plane k)
+                        self.bands[k].copy_(torch.from_numpy(b))
                     self.valid[k].copy_(torch.from_numpy(v))
         return Up()
 
@@ -287,7 +431,11 @@ class LocalJob:
                                             self.settings.get('label_rules', ()),
                                             self.pre_threshold_mode)
         numbers = list(st['band_numbers'])
-        prog = IndexProgram(self.settings['index_eqn'], band_dtype=st['bands'].dtype,
+        # the stack's sample type and shape: in device mode from the device stack (the host
+        # array's device-decoded planes are only filled when a caller reads stack['bands'])
+        meta = getattr(self, '_stack_meta', None)
+        b_dtype, b_shape = meta if meta is not None else (st['bands'].dtype, st['bands'].shape)
+        prog = IndexProgram(self.settings['index_eqn'], band_dtype=b_dtype,
                             raster_count=max(numbers))
         slots = [numbers.index(b) for b in prog.bands]  # the planes the equation reads
         fn = eng.compile_index(prog)
@@ -300,18 +448,20 @@ class LocalJob:
         # ranges) crosses to the device in one copy per array and each tile's inputs are made from
         # device views of it; 'tile': each tile's bands gathered into a host copy first (a 2 GB
         # single-threaded copy per 16.8 Mpx tile, most of round 6's job analysis time)
+        b_nbytes = int(np.prod(b_shape)) * np.dtype(b_dtype).itemsize
         whole = (cuda and os.environ.get('LT_JOB_UPLOAD', 'whole') == 'whole' and
-                 st['bands'].flags.c_contiguous and st['valid'].flags.c_contiguous and
-                 st['bands'].nbytes + st['valid'].nbytes <= (64 << 30))
+                 (meta is not None or st['bands'].flags.c_contiguous) and
+                 st['valid'].flags.c_contiguous and
+                 b_nbytes + st['valid'].nbytes <= (64 << 30))
         if whole:
             ds = getattr(self, '_dev_stack', None)
-            if ds is not None and ds[0].device == dev and ds[0].shape == st['bands'].shape:
+            if ds is not None and ds[0].device == dev and tuple(ds[0].shape) == tuple(b_shape):
                 w_bands, w_valid = ds  # uploaded raster by raster during parse()
             else:
                 w_bands = torch.from_numpy(st['bands']).to(dev)
                 w_valid = torch.from_numpy(st['valid']).to(dev)
             self._dev_stack = None
-            if slots != list(range(st['bands'].shape[1])):
+            if slots != list(range(b_shape[1])):
                 w_bands = w_bands[:, slots]
         items = []
         for t in m.mine:

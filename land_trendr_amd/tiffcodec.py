@@ -23,7 +23,7 @@ def _lib():
         if not os.path.exists(LIB_PATH):
             raise RuntimeError('%s not built: run __graft_entry__.build()' % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
-        for f in (L.lt_lzw_decode, L.lt_lzw_encode):
+        for f in (L.lt_lzw_decode, L.lt_lzw_encode, L.lt_lzw_decode_core):
             f.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64]
             f.restype = ctypes.c_int64
         i64, vp, ci = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
@@ -43,6 +43,16 @@ def lzw_decode(data, size):
     if n < 0:
         raise ValueError('LZW: corrupt strip (%d)' % n)
     out[n:] = 0  # (the decoder may leave scratch bytes past the end of a short strip)
+    return out
+
+
+def lzw_decode_core(data, size):
+    """lzw_decode by the decoder core the device runs (lt_lzw_core.h, host build): strips that
+    decode to less than 1 MiB."""
+    out = np.zeros(size, np.uint8)
+    n = _lib().lt_lzw_decode_core(bytes(data), len(data), out.ctypes.data, size)
+    if n < 0:
+        raise ValueError('LZW: corrupt strip (%d)' % n)
     return out
 
 

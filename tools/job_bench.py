@@ -14,6 +14,7 @@ would, on cuda:0, and the script prints one JSON line:
     compared with every output plane (the oracle is the checker here, never a producer).
 
     python tools/job_bench.py --rows 7000 --cols 7000 --years 30 [--trendline] [--check 20000]
+                              [--decode {host,device}]
 """
 import argparse
 import json
@@ -154,6 +155,9 @@ def main():
                          'cProfile of output() run again (stderr)')
     ap.add_argument('--profile', default=None, choices=('setup', 'parse', 'analyze', 'output'),
                     help='run this step under cProfile (top entries by own time to stderr)')
+    ap.add_argument('--decode', default='host', choices=('host', 'device'),
+                    help="where the rasters' strips are decoded (LocalJob decode=): liblt_io.so on "
+                         'the host threads, or the HIP strip decoder on the GPU')
     a = ap.parse_args()
     import torch
     from land_trendr_amd.ingest import host_threads
@@ -166,7 +170,7 @@ def main():
               flush=True)
         P = a.rows * a.cols
         j = LocalJob(a.work, 'bench', device=0, tile_pixels=a.tile, trendline=a.trendline,
-                     on_error='skip')
+                     on_error='skip', decode=a.decode)
         t = {}
         files = None
         for step in ('setup', 'parse', 'analyze', 'output'):
@@ -209,7 +213,10 @@ def main():
                'raster_order': j._raster_hw is not None,
                'jit': getattr(j, 'jit_stats', None),
                'analyze_parts_s': {k: round(v, 3) for k, v in getattr(j, 'analyze_s', {}).items()},
-               'upload': os.environ.get('LT_JOB_UPLOAD', 'whole')}
+               'upload': os.environ.get('LT_JOB_UPLOAD', 'whole'),
+               'decode': a.decode, 'decode_stats': j.decode_stats,
+               'decode_times_s': {k: round(v, 3)
+                                  for k, v in getattr(j, 'decode_times', {}).items()}}
         if a.diag:
             res['diag'] = diag(j)
         if a.check > 0:
