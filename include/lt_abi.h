@@ -360,6 +360,32 @@ typedef struct {
  * grown on demand). A failing strip's rows are unspecified; every other strip is decoded. */
 int lt_tiff_decode_strips_dev(lt_ctx* ctx, const lt_strips_job* jobs, int n_jobs, void* stream);
 
+/* ---- output: TIFF strips encoded on the device (an added export of ABI 8) -------------------------
+ * One raster in device memory to its strips: the arguments of lt_tiff_encode_strips
+ * (include/lt_io.h), every pointer a DEVICE pointer. */
+typedef struct {
+  const void* in;          /* DEVICE [bands][rows][cols], little-endian samples; never written     */
+  int32_t bands;
+  int32_t bps;             /* bytes per sample: 1, 2, 4, 8                                          */
+  int64_t rows, cols, rows_per_strip;
+  int32_t compression;     /* 1 or 5                                                                */
+  int32_t predictor;       /* 1 or 2 (horizontal differencing, integer wrap)                        */
+  uint8_t* out;            /* DEVICE [cap]: the strips back to back, band-major then row order      */
+  int64_t cap;
+  int64_t* strip_sizes;    /* DEVICE [ceil(rows / rows_per_strip) * bands]                          */
+  int64_t* total;          /* DEVICE one word: the bytes in `out`, or a negative LT_IO_ERR_*
+                              (LT_IO_ERR_SPACE when cap is too small: the strips that fit whole
+                              below cap are in place, nothing is written at or past out + cap)      */
+} lt_encode_job;
+/* lt_tiff_encode_strips (lt_io.h) for n_jobs rasters in device memory, asynchronous on `stream`:
+ * the same bytes, sizes and total. LT_ERR_ARG for what the host function rejects and for strips of
+ * 1 MiB or more of raw bytes. One lane per strip (the LZW core of land_trendr_amd/csrc/
+ * lt_lzw_core.h, the source liblt_io.so's lt_lzw_encode_core is compiled from), at most 32768 in
+ * flight; the context owns the lanes' dictionaries (32 KB a lane) and the slots they encode into
+ * (at most 1 GiB each, grown on demand); a scan and a packing kernel lay the strips out.
+ * Compression 1 is one coalesced kernel straight into `out`. */
+int lt_tiff_encode_strips_dev(lt_ctx* ctx, const lt_encode_job* jobs, int n_jobs, void* stream);
+
 /* Stage timing: when enabled, each lt_analyze_tile brackets its kernels with hipEvents on the
  * launch stream; lt_ctx_stage_ms returns the accumulated milliseconds per stage
  * (0 = analyze: every pixel with the lazy DP, 1 = resolve: the deferred pixels with the exact-OPT

@@ -28,6 +28,10 @@ int64_t lt_lzw_encode(const uint8_t* in, int64_t n_in, uint8_t* out, int64_t cap
  * counts, bytes and errors; LT_IO_ERR_ARG for cap >= 1 MiB (its table packs 20-bit positions);
  * no byte of out past the returned count is written. */
 int64_t lt_lzw_decode_core(const uint8_t* in, int64_t n_in, uint8_t* out, int64_t cap);
+/* lt_lzw_encode's contract by the encoder core the device runs (lt_lzw_core.h, one lane per strip
+ * in lt_tiff_encode_strips_dev), compiled for the host: the same bytes for every input; no byte
+ * of out at or past cap, and none past the returned count, is written. */
+int64_t lt_lzw_encode_core(const uint8_t* in, int64_t n_in, uint8_t* out, int64_t cap);
 
 /* Every strip of one strip-organised TIFF image decoded on `threads` threads into `out`, the
  * [bands, height, width] samples in native byte order (what ds2array gives per band,

@@ -158,6 +158,15 @@ class LtStripsJob(ctypes.Structure):
                 ('err', ctypes.c_void_p)]
 
 
+class LtEncodeJob(ctypes.Structure):
+    """lt_encode_job: one raster in device memory to its TIFF strips."""
+    _fields_ = [('in_', ctypes.c_void_p), ('bands', ctypes.c_int32), ('bps', ctypes.c_int32),
+                ('rows', ctypes.c_int64), ('cols', ctypes.c_int64),
+                ('rows_per_strip', ctypes.c_int64), ('compression', ctypes.c_int32),
+                ('predictor', ctypes.c_int32), ('out', ctypes.c_void_p), ('cap', ctypes.c_int64),
+                ('strip_sizes', ctypes.c_void_p), ('total', ctypes.c_void_p)]
+
+
 class LtIndexIO(ctypes.Structure):
     _fields_ = [('n_pix', ctypes.c_int64), ('n_obs', ctypes.c_int64),
                 ('obs_stride', ctypes.c_int64), ('band_stride', ctypes.c_int64),
@@ -194,7 +203,8 @@ EXPORTS = ['lt_abi_version', 'lt_ctx_create', 'lt_ctx_destroy', 'lt_last_error',
            'lt_ctx_last_deferred', 'lt_index_codegen', 'lt_index_compile', 'lt_index_apply',
            'lt_settings_compile', 'lt_raster_assemble', 'lt_winner_presence',
            'lt_index_linearize', 'lt_ctx_set_jit_mode', 'lt_jit_prepare', 'lt_ctx_jit_stats',
-           'lt_jit_source', 'lt_analyze_tiles_ev', 'lt_tiff_decode_strips_dev']
+           'lt_jit_source', 'lt_analyze_tiles_ev', 'lt_tiff_decode_strips_dev',
+           'lt_tiff_encode_strips_dev']
 
 LT_JIT_SYNC, LT_JIT_ASYNC = 0, 1
 LT_JIT_SRC_SPEC, LT_JIT_SRC_SCENE, LT_JIT_SRC_FIELDS = 1, 2, 4
@@ -272,6 +282,7 @@ def load_lib(path=None):
                                   ctypes.c_int32, ctypes.c_char_p, ctypes.c_int64]
     lib.lt_jit_source.restype = ctypes.c_int
     lib.lt_tiff_decode_strips_dev.argtypes = [vp, ctypes.POINTER(LtStripsJob), ctypes.c_int, vp]
+    lib.lt_tiff_encode_strips_dev.argtypes = [vp, ctypes.POINTER(LtEncodeJob), ctypes.c_int, vp]
     if lib.lt_abi_version() != LT_ABI_VERSION:
         raise RuntimeError('liblt_hip.so ABI %d != %d' % (lib.lt_abi_version(), LT_ABI_VERSION))
     if path is None:

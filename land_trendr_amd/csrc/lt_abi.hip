@@ -305,6 +305,7 @@ struct lt_ctx {
   // 8.1 ms alone (28 GB of rows at 3.5 TB/s) and gets CU slots only between analyze launches
   bool tl_split = false;
   lt::DecodeScratch dec;  // the strip decoder's scratch (lt_decode.hip)
+  lt::EncodeScratch enc;  // the strip encoder's scratch (lt_encode.hip)
 };
 
 static int fail(lt_ctx* c, int code, const char* fmt, const char* detail = "") {
@@ -316,8 +317,9 @@ static int fail(lt_ctx* c, int code, const char* fmt, const char* detail = "") {
   return code;
 }
 
-namespace lt {  // the context as lt_decode.hip sees it (lt_launch.h)
+namespace lt {  // the context as lt_decode.hip and lt_encode.hip see it (lt_launch.h)
 DecodeScratch& ctx_decode(lt_ctx* c) { return c->dec; }
+EncodeScratch& ctx_encode(lt_ctx* c) { return c->enc; }
 int ctx_device(const lt_ctx* c) { return c->device; }
 int ctx_fail(lt_ctx* c, int code, const char* fmt, const char* detail) {
   return fail(c, code, fmt, detail);
@@ -428,6 +430,7 @@ int lt_ctx_destroy(lt_ctx* c) {
   if (c->d_scene) (void)hipFree(c->d_scene);
   if (c->d_xtab) (void)hipFree(c->d_xtab);
   lt::decode_release(c->dec);
+  lt::encode_release(c->enc);
   for (auto& kv : c->index_fns) {
     if (kv.second->mod) (void)hipModuleUnload(kv.second->mod);
     delete kv.second;

@@ -423,4 +423,11 @@ int64_t lt_lzw_decode_core(const uint8_t* in, int64_t n_in, uint8_t* out, int64_
   return lt_lzw::decode(in, n_in, out, cap, lt_lzw::FlatTable{table});
 }
 
+// The encoder core the device runs (lt_lzw_core.h, lt_encode.hip), compiled for the host:
+// lt_lzw_encode's bytes from the open-addressing dictionary a lane can afford.
+int64_t lt_lzw_encode_core(const uint8_t* in, int64_t n_in, uint8_t* out, int64_t cap) {
+  uint32_t table[lt_lzw::kEncSlots];
+  return lt_lzw::encode(in, n_in, out, cap, lt_lzw::FlatTable{table});
+}
+
 }  // extern "C"

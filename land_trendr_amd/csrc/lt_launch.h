@@ -1,5 +1,5 @@
 // lt_launch.h — what lt_abi.hip hands the analyze-stage dispatch for one tile, and what it shares
-// with the strip decoder (lt_decode.hip).
+// with the strip decoder (lt_decode.hip) and the strip encoder (lt_encode.hip).
 //
 // The kernels of the analyze and resolve stages (lt_kernels.h) are instantiated in a dispatch
 // translation unit of their own: lt_dispatch.hip in the product library, a profiling unit in the
@@ -47,8 +47,26 @@ struct DecodeScratch {
   int n_sets = 0;
 };
 void decode_release(DecodeScratch& s);
-// What lt_decode.hip needs of a context (defined in lt_abi.hip beside lt_ctx).
+// The strip encoder's share of a context (lt_encode.hip, lt_tiff_encode_strips_dev): scratch grown
+// on demand, freed with the context (encode_release), one set per stream like the decoder's.
+struct EncodeScratch {
+  struct Set {
+    uint32_t* d_tables = nullptr;  // the lanes' LZW dictionaries: [waves][8192 slots][64 lanes]
+    int64_t table_lanes = 0;
+    uint8_t* d_slots = nullptr;    // one worst-case encoded strip per lane
+    int64_t slots_bytes = 0;
+    void* d_meta = nullptr;        // per lane a size and an offset, per job a total and an error
+  };
+  static constexpr int kMaxSets = 16;
+  static constexpr int64_t kMaxLanes = 32768;  // in flight: 1 GiB of dictionaries
+  hipStream_t stream[kMaxSets] = {};
+  Set set[kMaxSets];
+  int n_sets = 0;
+};
+void encode_release(EncodeScratch& s);
+// What lt_decode.hip and lt_encode.hip need of a context (defined in lt_abi.hip beside lt_ctx).
 DecodeScratch& ctx_decode(lt_ctx* c);
+EncodeScratch& ctx_encode(lt_ctx* c);
 int ctx_device(const lt_ctx* c);
 int ctx_fail(lt_ctx* c, int code, const char* fmt, const char* detail);
 

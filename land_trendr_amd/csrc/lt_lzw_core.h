@@ -1,5 +1,6 @@
-// lt_lzw_core.h — one TIFF LZW strip decoder, compiled for the host (g++: lt_io.cpp's
-// lt_lzw_decode_core) and for the device (hipcc: lt_decode.hip, one lane per strip).
+// lt_lzw_core.h — one TIFF LZW strip decoder and one encoder (below it), compiled for the host
+// (g++: lt_io.cpp's lt_lzw_decode_core / lt_lzw_encode_core) and for the device (hipcc:
+// lt_decode.hip and lt_encode.hip, one lane per strip).
 //
 // The stream rules are those at the top of lt_io.cpp: codes MSB first, 9 to 12 bits wide, Clear 256,
 // EOI 257, first free code 258, libtiff's early change, a strip may end without EOI, data starts
@@ -128,6 +129,130 @@ LT_LZW_HD inline int64_t decode(const uint8_t* in, int64_t n_in, uint8_t* out, i
     }
   }
   return n_out;
+}
+
+// ---- the encoder ---------------------------------------------------------------------------------
+// lt_lzw_encode's code stream (lt_io.cpp), byte for byte: Clear first, 9..12-bit codes MSB first,
+// libtiff's early change, a Clear when free_ent reaches 4094, after the final code a Clear when the
+// table just filled or else the width step, then EOI; n_in == 0 gives Clear, EOI. Greedy LZW under
+// these rules is deterministic, so only the dictionary differs from the host's 4096 x 256 direct
+// table: open addressing (linear probing) over kEncSlots 32-bit words, one word per string:
+// prefix code (12 bits) | byte (8 bits) | code (12 bits). A code is at least 258, so 0 is an empty
+// slot. At most 3836 strings exist between two Clears (codes 258..4093): the load stays at or below
+// 3836 / 8192 and an empty slot always ends a probe sequence. The caller owns the table and hands
+// it in through an accessor with get(slot) / set(slot, word) for slots 0..kEncSlots-1 (FlatTable,
+// StridedTable); it is zeroed here at the start and at each Clear, slot by slot in order, which on
+// the device is one coalesced store per slot for the lanes of a wave.
+//
+// The input is read through a byte source, byte(k) for k in [0, n_in), so the device applies
+// predictor 2 on the fly (never to the raster). Every loop is bounded by the arguments alone: the
+// byte loop by n_in, a probe sequence by kEncSlots with an explicit counter, the zeroing by
+// kEncSlots, the bit writer by cap. Never a write at or past out + cap. Returns the byte count, or
+// kErrArg / kErrSpace (cap too small: out's contents are then unspecified).
+constexpr int kEncSlots = 8192;  // per encoder: 32 KB
+
+struct PlainBytes {
+  const uint8_t* p;
+  LT_LZW_HD uint8_t byte(int64_t k) const { return p[k]; }
+};
+
+// the pending bits, the oldest most significant; whole bytes leave as soon as they are complete
+struct EncBits {
+  uint8_t* out;
+  int64_t cap, n;
+  uint32_t acc;
+  int nacc;  // below 8 between two puts
+  LT_LZW_HD bool put(int code, int nbits) {  // false: out of space
+    acc = (acc << nbits) | (uint32_t)code;  // at most 7 + 12 bits
+    nacc += nbits;
+    while (nacc >= 8) {  // at most two bytes
+      if (n >= cap) return false;
+      nacc -= 8;
+      out[n++] = (uint8_t)(acc >> nacc);
+    }
+    acc &= (1u << nacc) - 1u;
+    return true;
+  }
+  LT_LZW_HD bool flush() {
+    if (nacc > 0) {
+      if (n >= cap) return false;
+      out[n++] = (uint8_t)(acc << (8 - nacc));
+    }
+    nacc = 0;
+    acc = 0;
+    return true;
+  }
+};
+
+template <class Table>
+LT_LZW_HD inline void enc_zero(const Table tab) {
+  for (int s = 0; s < kEncSlots; s++) tab.set(s, 0u);
+}
+
+template <class Src, class Table>
+LT_LZW_HD inline int64_t encode_from(const Src src, int64_t n_in, uint8_t* out, int64_t cap,
+                                     const Table tab) {
+  constexpr int kClear = 256, kEoi = 257, kFirst = 258, kMaxBits = 12;
+  if (n_in < 0 || cap < 0 || (cap > 0 && !out)) return kErrArg;
+  EncBits w{out, cap, 0, 0u, 0};
+  int nbits = 9, free_ent = kFirst;
+  if (!w.put(kClear, nbits)) return kErrSpace;
+  if (n_in == 0) {
+    if (!w.put(kEoi, nbits) || !w.flush()) return kErrSpace;
+    return w.n;
+  }
+  enc_zero(tab);
+  int ent = src.byte(0);
+  for (int64_t k = 1; k < n_in; k++) {
+    const int c = src.byte(k);
+    const uint32_t key = ((uint32_t)ent << 8) | (uint32_t)c;  // 20 bits
+    uint32_t h = (key * 2654435761u) >> 19;                   // 13 bits
+    int found = -1;
+    int probes = 0;
+    for (; probes < kEncSlots; probes++) {
+      const uint32_t e = tab.get((int)h);
+      if (e == 0u) break;
+      if ((e >> 12) == key) {
+        found = (int)(e & 0xfffu);
+        break;
+      }
+      h = (h + 1u) & (uint32_t)(kEncSlots - 1);
+    }
+    if (found >= 0) {  // the string ent + c is in the table
+      ent = found;
+      continue;
+    }
+    if (probes == kEncSlots) return kErrArg;  // (never: the table is at most 3836 / 8192 full)
+    if (!w.put(ent, nbits)) return kErrSpace;
+    tab.set((int)h, (key << 12) | (uint32_t)free_ent);  // ent + c gets the next code
+    free_ent++;
+    ent = c;
+    if (free_ent == (1 << kMaxBits) - 2) {  // table full (4094 codes): Clear, restart at 9 bits
+      if (!w.put(kClear, nbits)) return kErrSpace;
+      nbits = 9;
+      free_ent = kFirst;
+      enc_zero(tab);
+    } else if (free_ent > (1 << nbits) - 1) {
+      nbits++;
+    }
+  }
+  if (!w.put(ent, nbits)) return kErrSpace;
+  free_ent++;
+  if (free_ent == (1 << kMaxBits) - 2) {
+    if (!w.put(kClear, nbits)) return kErrSpace;
+    nbits = 9;
+  } else if (free_ent > (1 << nbits) - 1) {
+    nbits++;
+  }
+  if (!w.put(kEoi, nbits) || !w.flush()) return kErrSpace;
+  return w.n;
+}
+
+template <class Table>
+LT_LZW_HD inline int64_t encode(const uint8_t* in, int64_t n_in, uint8_t* out, int64_t cap,
+                                const Table tab) {
+  if (!in) return kErrArg;
+  return encode_from(PlainBytes{in}, n_in, out, cap, tab);
 }
 
 }  // namespace lt_lzw

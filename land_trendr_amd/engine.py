@@ -46,6 +46,7 @@ class Engine:
             raise LtError('lt_ctx_create failed (%d)' % rc)
         self.ctx = ctx
         self._decode_lock = threading.Lock()
+        self._encode_lock = threading.Lock()
 
     def close(self):
         if self.ctx:
@@ -351,6 +352,66 @@ class Engine:
                                                            ctypes.c_void_p(st.cuda_stream)),
                         'lt_tiff_decode_strips_dev')
         return outs, err[:n]
+
+    # --- output: TIFF strips encoded on the device (lt_tiff_encode_strips_dev, lt_encode.hip) ---
+    def encode_strips(self, jobs, stream=None):
+        """The LZW / uncompressed strips of len(jobs) rasters in device memory, encoded by the HIP
+        strip encoder in one call: tiffcodec.encode_strips's bytes and sizes. A job is a dict:
+          data      contiguous device tensor [bands, rows, cols] or [rows, cols] (1, 2, 4 or 8
+                    byte samples; never written);
+          rows_per_strip, compression (1 or 5), predictor (1 or 2; 2 for integer samples);
+          out       optional uint8 device tensor to fill (default: the worst case);
+          cap       optional: only the first cap bytes of out are offered.
+        Returns, per job, (out uint8 tensor, strip_sizes int64 tensor, total int64 tensor of one
+        element: the bytes in out, or a negative LT_IO_ERR_*, LT_IO_ERR_SPACE when cap is too
+        small). Asynchronous on `stream`; the caller keeps `data` alive until it has run."""
+        n = len(jobs)
+        arr = (_abi.LtEncodeJob * max(n, 1))()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        res = []
+        for k, j in enumerate(jobs):
+            d = j['data']
+            if (not isinstance(d, torch.Tensor) or d.device != self.device or
+                    d.dim() not in (2, 3) or not d.is_contiguous() or d.numel() == 0 or
+                    d.is_complex() or d.element_size() not in (1, 2, 4, 8)):
+                raise LtError('encode_strips: data must be a contiguous [bands, rows, cols] or '
+                              '[rows, cols] tensor of 1, 2, 4 or 8 byte samples on %s'
+                              % self.device)
+            nb, rows, cols = (1,) + tuple(d.shape) if d.dim() == 2 else tuple(d.shape)
+            rps, comp, pred = (int(j['rows_per_strip']), int(j['compression']),
+                               int(j.get('predictor', 1)))
+            if rps <= 0 or comp not in (1, 5) or pred not in (1, 2):
+                raise LtError('encode_strips: rows_per_strip > 0, compression 1 or 5, '
+                              'predictor 1 or 2')
+            if pred == 2 and d.is_floating_point():
+                raise LtError('encode_strips: predictor 2 is for integer samples')
+            ns = nb * (-(-rows // rps))
+            raw = nb * rows * cols * d.element_size()
+            out = j.get('out')
+            with torch.cuda.stream(st):  # (tensors made here belong to the stream that fills them)
+                if out is None:
+                    out = torch.empty(raw * 3 // 2 + 16 * ns + 16 if comp == 5 else raw,
+                                      dtype=torch.uint8, device=self.device)
+                meta = torch.empty(ns + 1, dtype=torch.int64, device=self.device)
+            if (out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or
+                    out.device != self.device):
+                raise LtError('encode_strips: out must be a contiguous uint8 tensor on %s'
+                              % self.device)
+            cap = int(j['cap']) if j.get('cap') is not None else out.numel()
+            if cap < 0 or cap > out.numel():
+                raise LtError('encode_strips: cap must be within out')
+            a = arr[k]
+            a.in_, a.bands, a.bps = d.data_ptr(), nb, d.element_size()
+            a.rows, a.cols, a.rows_per_strip = rows, cols, rps
+            a.compression, a.predictor = comp, pred
+            a.out, a.cap = out.data_ptr(), cap
+            a.strip_sizes, a.total = meta.data_ptr(), meta.data_ptr() + 8 * ns
+            res.append((out, meta[:ns], meta[ns:]))
+        with self._encode_lock:  # one context: one caller at a time
+            self._check(self.lib.lt_tiff_encode_strips_dev(self.ctx, arr, n,
+                                                           ctypes.c_void_p(st.cuda_stream)),
+                        'lt_tiff_encode_strips_dev')
+        return res
 
     # --- JIT kernels of tiles carrying a program (lt_jit.h; lt_ctx_set_jit_mode, lt_jit_prepare) ---
     def set_jit_mode(self, asynchronous):

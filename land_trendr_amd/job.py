@@ -85,14 +85,19 @@ class _LazyBands(dict):
 class LocalJob:
     def __init__(self, root, job, device=None, tile_pixels=1 << 22, trendline=True,
                  raster_mode='reference', pre_threshold_mode='reference', on_error='raise',
-                 work_dir=None, engine=None, decode=None):
+                 work_dir=None, engine=None, decode=None, encode=None):
         """engine: the analysis engine (default: engine.get_engine of `device`, the HIP library);
         tests pass a CPU double (tests/engine_double.py) to run the multi-rank path over gloo.
         decode: 'host' (default; LT_JOB_DECODE overrides the default) — every raster's strips are
         decoded by liblt_io.so on the host threads; 'device' — parse() builds the device stack up
         front and the rasters the HIP strip decoder takes (GeoTiff.device_eligible, read in
         place: raster order, every band) are decoded on the GPU straight into it, the others on
-        the host as before; decode_stats counts both."""
+        the host as before; decode_stats counts both.
+        encode: 'host' (default; LT_JOB_ENCODE overrides the default) — output() encodes every
+        raster's strips with liblt_io.so on the host threads; 'device' — where output() assembles
+        the rasters on the GPU, the HIP strip encoder (Engine.encode_strips) encodes each assembled
+        batch there and only the strips come down; elsewhere (a CPU engine, host assembly) the
+        host encoder as before; encode_stats counts the rasters by path."""
         if on_error not in ('raise', 'skip'):
             raise ValueError('on_error must be "raise" or "skip"')
         decode = decode or os.environ.get('LT_JOB_DECODE') or 'host'
@@ -100,6 +105,11 @@ class LocalJob:
             raise ValueError('decode must be "host" or "device"')
         self.decode = decode
         self.decode_stats = {'device': 0, 'host': 0}  # rasters by the path that decoded them
+        encode = encode or os.environ.get('LT_JOB_ENCODE') or 'host'
+        if encode not in ('host', 'device'):
+            raise ValueError('encode must be "host" or "device"')
+        self.encode = encode
+        self.encode_stats = {'device': 0, 'host': 0}  # rasters by the path that encoded them
         self.decode_times = {}  # device mode: thread-seconds of parse() inside the decoder
         self._stack_meta = None  # device mode: (sample type, [K, nb, Q]) of the device stack
         self._dev_keep = None    # device mode: the device stack behind stack['bands']
@@ -643,8 +653,9 @@ class LocalJob:
         finished GDT_Byte (or typed) array, written at once; a grid that maps two points to one
         pixel (the reference's loop: the last one wins) is assembled on the host."""
         import torch
-        from .raster import (label_rasters, label_rasters_device, output_reducer,
-                             trendline_rasters, trendline_rasters_device)
+        from .raster import (_np_dtype, _strip_rows, device_encodable, label_rasters,
+                             label_rasters_device, output_reducer, raster_path,
+                             trendline_rasters, trendline_rasters_device, write_tiff_strips)
         tmpl = GeoTiff(self.rast_fns[0])
         rows, cols = tmpl.height, tmpl.width
         lng, lat = self.grid_xy
@@ -680,23 +691,85 @@ class LocalJob:
                 while len(inflight) > keep:
                     out.update(inflight.popleft().result())
 
+            stats = {'device': 0, 'host': 0}
+
             def write(key, arr):  # each raster to its file as soon as it is on the host
+                stats['host'] += 1
                 inflight.append(writer.submit(
                     lambda r: dict(output_reducer(r, tmpl, self.root, self.job)), {key: arr}))
                 settle(2)
 
+            # encode='device': each assembled batch (a rule set's rasters, one date's attributes)
+            # is encoded by the HIP strip encoder on the same stream, every raster with its own
+            # sample type and rows per strip (raster_mode 'typed' mixes int32, float64 and uint8);
+            # the sizes and totals of the batch come down in one copy, then per raster exactly
+            # `total` bytes into one of three pinned buffers, and the writer thread only lays out
+            # the header and writes. A raster the encoder does not take goes through write().
+            ring = [None] * 3
+            turn = [0]
+
+            def put(path, buf, n, sizes, dtype, rps, ev, keep):
+                ev.synchronize()
+                write_tiff_strips(path, buf[:n].numpy(), sizes, (1, rows, cols), dtype, 5, 1,
+                                  rps, tmpl)
+                return {keep[0]: [path]}
+
+            def encode_batch(batch):
+                plan = []  # per raster: (numpy sample type, rows per strip) or None (host)
+                for _, t in batch:
+                    ndt = _np_dtype(t)
+                    plan.append((ndt, _strip_rows(rows, cols, ndt.itemsize))
+                                if device_encodable(ndt, (rows, cols)) else None)
+                took = [i for i, p in enumerate(plan) if p is not None]
+                enc = self.engine.encode_strips(
+                    [{'data': batch[i][1], 'rows_per_strip': plan[i][1], 'compression': 5,
+                      'predictor': 1} for i in took]) if took else []
+                # one copy for the sizes and totals of the whole batch
+                flat = (torch.cat([x for _, sizes, total in enc for x in (sizes, total)])
+                        .cpu().numpy() if took else None)
+                metas, o = {}, 0
+                for i, (_, sizes, _) in zip(took, enc):
+                    metas[i] = flat[o:o + sizes.numel() + 1]
+                    o += sizes.numel() + 1
+                    if int(metas[i][-1]) < 0:
+                        raise ValueError('TIFF strips: device encode failed (%d)'
+                                         % int(metas[i][-1]))
+                need = max([1 << 20] + [int(m[-1]) for m in metas.values()])
+                eouts = {i: e[0] for i, e in zip(took, enc)}
+                for i, (key, t) in enumerate(batch):
+                    if plan[i] is None:
+                        write(key, t.cpu().numpy())
+                        continue
+                    ndt, rps = plan[i]
+                    n = int(metas[i][-1])
+                    settle(2)  # the buffer of three rasters ago is written out
+                    k = turn[0] % 3
+                    turn[0] += 1
+                    if ring[k] is None or ring[k].numel() < need:
+                        ring[k] = torch.empty(need, dtype=torch.uint8).pin_memory()
+                    ring[k][:n].copy_(eouts[i][:n], non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record(torch.cuda.current_stream(self.engine.device))
+                    stats['device'] += 1
+                    inflight.append(writer.submit(
+                        put, raster_path(self.root, self.job, key), ring[k], n, metas[i][:-1],
+                        ndt, rps, ev, (key, eouts[i])))
+
+            dsink = encode_batch if self.encode == 'device' else None
             try:
                 for k, a in label_rasters_device(self.engine, dp, self.rules, (rows, cols), ddest,
-                                                 tdt, self.raster_mode).items():
+                                                 tdt, self.raster_mode,
+                                                 device_sink=dsink).items():
                     write(k, a)
                 if self.trendline:
                     rows_dev = _DeviceRows(self.host_trendline, dp['status'].device)
                     trendline_rasters_device(self.engine, rows_dev, self.scene, self.scene.dates,
                                              (rows, cols), ddest, tdt, self.raster_mode,
-                                             sink=write)
+                                             sink=write, device_sink=dsink)
                 settle(0)
             finally:
                 writer.shutdown(wait=True)
+            self.encode_stats = stats
             self._join_grid()  # the grid CSV, the job's other output, in place too
             return out
         n = rows * cols
@@ -711,6 +784,7 @@ class LocalJob:
             rasters.update(trendline_rasters(placed, self.scene, self.scene.dates, (rows, cols),
                                              tdt, self.raster_mode))
         res = dict(output_reducer(rasters, tmpl, self.root, self.job))
+        self.encode_stats = {'device': 0, 'host': len(res)}
         self._join_grid()
         return res
 

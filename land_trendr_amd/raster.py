@@ -130,6 +130,12 @@ def _np(t):
     return np.asarray(t)
 
 
+def _np_dtype(t):
+    """The numpy sample type of a torch tensor."""
+    import torch
+    return torch.empty(0, dtype=t.dtype).numpy().dtype
+
+
 # ---- GeoTIFF writer ----------------------------------------------------------------------------
 _SAMPLE_FORMAT = {'u': 1, 'i': 2, 'f': 3}
 _GEO_TAGS = (33550, 33922, 34264, 34735, 34736, 34737)  # scale, tiepoint, transform, geokeys ...
@@ -156,14 +162,11 @@ def write_geotiff(path, array, template=None, nodata=NODATA, geotransform=None, 
         a = a[None]
     nb, rows, cols = a.shape
     tmpl = GeoTiff(template) if isinstance(template, str) else template
-    rps = rows_per_strip or max(1, min(rows, 8192 // max(1, cols * a.dtype.itemsize)))
+    rps = _strip_rows(rows, cols, a.dtype.itemsize, rows_per_strip)
     if tiffcodec.native_strips(comp, predictor, a.dtype.itemsize * 8):
         # every strip on the host's threads (liblt_io.so lt_tiff_encode_strips)
         from .ingest import host_threads
         data, sizes = tiffcodec.encode_strips(a, rps, comp, predictor, host_threads())
-        bounds = np.concatenate([[0], np.cumsum(sizes)])
-        mv = memoryview(data)
-        strips = [mv[bounds[k]:bounds[k + 1]] for k in range(len(sizes))]
     else:
         strips = []
         for b in range(nb):
@@ -172,6 +175,25 @@ def write_geotiff(path, array, template=None, nodata=NODATA, geotransform=None, 
                 if predictor == 2:
                     blk = tiffcodec.apply_predictor2(blk, cols, 1)
                 strips.append(tiffcodec.encode(comp, np.ascontiguousarray(blk).tobytes()))
+        data, sizes = b''.join(strips), [len(st) for st in strips]
+    return write_tiff_strips(path, data, sizes, (nb, rows, cols), a.dtype, comp, predictor, rps,
+                             tmpl, geotransform, nodata)
+
+
+def write_tiff_strips(path, data, sizes, shape, dtype, comp, predictor, rps, tmpl=None,
+                      geotransform=None, nodata=NODATA):
+    """The file write_geotiff lays out, from strips that are already encoded: `data` holds them
+    back to back (band-major, then row order; a bytes-like object or a uint8 array of exactly
+    sum(sizes) bytes), `sizes` their byte counts; shape (bands, rows, cols), dtype the sample
+    type, comp / predictor the TIFF tag values the strips were encoded with, rps the rows per
+    strip, tmpl a GeoTiff or None."""
+    nb, rows, cols = shape
+    dtype = np.dtype(dtype)
+    sizes = [int(v) for v in sizes]
+    total = sum(sizes)
+    if len(data) != total:
+        raise ValueError('write_tiff_strips: %d bytes of strips, sizes add up to %d'
+                         % (len(data), total))
 
     def layout(data_off):
         entries = []  # (tag, type, count, payload bytes)
@@ -181,22 +203,22 @@ def write_geotiff(path, array, template=None, nodata=NODATA, geotransform=None, 
             entries.append((tag, typ, len(values), payload))
 
         offs, o = [], data_off
-        for st in strips:
+        for m in sizes:
             offs.append(o)
-            o += len(st)
+            o += m
         add(256, 4, [cols], 'I')
         add(257, 4, [rows], 'I')
-        add(258, 3, [a.dtype.itemsize * 8] * nb, 'H')
+        add(258, 3, [dtype.itemsize * 8] * nb, 'H')
         add(259, 3, [comp], 'H')
         add(262, 3, [1], 'H')
         add(273, 4, offs, 'I')
         add(277, 3, [nb], 'H')
         add(278, 4, [rps], 'I')
-        add(279, 4, [len(st) for st in strips], 'I')
+        add(279, 4, sizes, 'I')
         add(284, 3, [2 if nb > 1 else 1], 'H')
         if predictor == 2:
             add(317, 3, [2], 'H')
-        add(339, 3, [_SAMPLE_FORMAT[a.dtype.kind]] * nb, 'H')
+        add(339, 3, [_SAMPLE_FORMAT[dtype.kind]] * nb, 'H')
         if tmpl is not None:
             for tag in _GEO_TAGS:
                 if tag in tmpl.tags:
@@ -239,18 +261,81 @@ def write_geotiff(path, array, template=None, nodata=NODATA, geotransform=None, 
     data_off = layout(0)[3]
     ifd_off, ifd, extra, end = layout(data_off)
     assert end == data_off
-    if data_off + sum(len(st) for st in strips) >= 1 << 32:
+    if data_off + total >= 1 << 32:
         raise ValueError('write_geotiff: over 4 GiB needs BigTIFF, which is not written')
     with open(path, 'wb') as f:
         f.write(b'II*\x00' + struct.pack('<I', ifd_off))
         f.write(ifd)
         f.write(extra)
         f.write(b'\x00' * (data_off - ifd_off - len(ifd) - len(extra)))
-        if strips and isinstance(strips[0], memoryview):  # back to back already
-            f.write(strips[0].obj[:sum(len(st) for st in strips)])
-        else:
-            for st in strips:
-                f.write(st)
+        f.write(data)
+    return path
+
+
+def _strip_rows(rows, cols, itemsize, rows_per_strip=None):
+    """write_geotiff's rows per strip: about 8 KB of raw samples, as GDAL's GTiff driver does."""
+    return rows_per_strip or max(1, min(rows, 8192 // max(1, cols * itemsize)))
+
+
+def device_encodable(dtype, shape, compress='lzw', predictor=1, rows_per_strip=None):
+    """Whether write_geotiff_device encodes this raster on the device: LZW or no compression,
+    predictor 1 or 2, 1, 2, 4 or 8 byte samples, strips of less than 1 MiB of raw bytes. Anything
+    else is write_geotiff's, which writes Deflate and large strips on the host and raises
+    ValueError for what it does not write either (float samples with predictor 2)."""
+    dtype = np.dtype(dtype)
+    if compress not in (None, 'none', 'lzw') or dtype.kind not in _SAMPLE_FORMAT:
+        return False
+    if predictor not in (1, 2) or (predictor == 2 and dtype.kind == 'f'):
+        return False
+    if dtype.itemsize not in (1, 2, 4, 8) or len(shape) not in (2, 3):
+        return False
+    rows, cols = shape[-2], shape[-1]
+    if rows <= 0 or cols <= 0:
+        return False
+    rps = _strip_rows(rows, cols, dtype.itemsize, rows_per_strip)
+    return min(rps, rows) * cols * dtype.itemsize < 1 << 20
+
+
+def write_geotiff_device(path, tensor, engine, template=None, nodata=NODATA, geotransform=None,
+                         compress='lzw', predictor=1, rows_per_strip=None, stream=None):
+    """write_geotiff for a raster in device memory: its strips are encoded on the GPU
+    (Engine.encode_strips), the sizes and the total come down, then exactly `total` bytes, and
+    the file is byte-identical to write_geotiff's for the same array and arguments. What the
+    device encoder does not take (device_encodable: Deflate, strips of 1 MiB or more) is copied
+    down and handed to write_geotiff, whose ValueError for float samples with predictor 2 is
+    raised here too. stream: the stream `tensor` was produced on (default: the current one);
+    the encode and the copies down run on it."""
+    import torch
+    a_dt = _np_dtype(tensor)
+    if not device_encodable(a_dt, tuple(tensor.shape), compress, predictor, rows_per_strip) or \
+            torch.device(engine.device).type != 'cuda':
+        return write_geotiff(path, _np(tensor), template, nodata, geotransform, compress,
+                             predictor, rows_per_strip)
+    st = stream if stream is not None else torch.cuda.current_stream(engine.device)
+    with torch.cuda.stream(st):
+        t = tensor.contiguous()
+    nb, rows, cols = (1,) + tuple(t.shape) if t.dim() == 2 else tuple(t.shape)
+    comp = {None: 1, 'none': 1, 'lzw': 5}[compress]
+    rps = _strip_rows(rows, cols, a_dt.itemsize, rows_per_strip)
+    (out, sizes, total), = engine.encode_strips(
+        [{'data': t, 'rows_per_strip': rps, 'compression': comp, 'predictor': predictor}], st)
+    with torch.cuda.stream(st):  # the copies down follow the encode on its stream
+        meta = torch.cat([sizes, total]).cpu().numpy()
+        n = int(meta[-1])
+        if n < 0:
+            raise ValueError('TIFF strips: device encode failed (%d)' % n)
+        data = out[:n].cpu().numpy()
+    tmpl = GeoTiff(template) if isinstance(template, str) else template
+    return write_tiff_strips(path, data, meta[:-1], (nb, rows, cols), a_dt, comp, predictor, rps,
+                             tmpl, geotransform, nodata)
+
+
+def raster_path(out_dir, job, key):
+    """<out_dir>/<job>/output/rasters/<key>.tif (settings.py OUT_RAST_KEYNAME), its directory
+    made."""
+    import os
+    path = os.path.join(out_dir, '%s/output/rasters/%s.tif' % (job, key))
+    os.makedirs(os.path.dirname(path), exist_ok=True)
     return path
 
 
@@ -261,8 +346,7 @@ def output_reducer(rasters, template, out_dir, job='job', compress='lzw'):
     import os
     tmpl = GeoTiff(template) if isinstance(template, str) else template
     for key in sorted(rasters):
-        path = os.path.join(out_dir, '%s/output/rasters/%s.tif' % (job, key))
-        os.makedirs(os.path.dirname(path), exist_ok=True)
+        path = raster_path(out_dir, job, key)
         write_geotiff(path, rasters[key], template=tmpl, compress=compress)
         yield key, [path]
 
@@ -285,11 +369,13 @@ def _job(n_pix, n_out, plane, sel_kind, sel, sel_value, holder_t, const_value, d
 
 
 def label_rasters_device(engine, planes, rules, shape, dest=None, template_dtype=np.int16,
-                         mode='reference'):
+                         mode='reference', device_sink=None):
     """label_rasters for [R, P] planes in device memory (matched, onset_year, duration,
     magnitude): each '<rule>_<field>' raster is assembled by lt_raster_assemble and only the
     finished raster is copied to the host. dest: None (grid point p is raster pixel p) or a device
-    int64 [P] of distinct raster offsets. Same values as label_rasters on the host planes."""
+    int64 [P] of distinct raster offsets. Same values as label_rasters on the host planes.
+    device_sink: when given, device_sink([(key, [rows, cols] device tensor), ...]) receives the
+    assembled rasters in one batch instead (nothing is copied down here; returns {})."""
     import torch
     from .index_eqn import DTYPES
     rows, cols = shape
@@ -311,16 +397,21 @@ def label_rasters_device(engine, planes, rules, shape, dest=None, template_dtype
                               torch.float64: _abi.LT_T_F64}[typ], out))
             res['%s_%s' % (rule.name, key)] = out
     engine.raster_assemble(jobs)
+    if device_sink is not None:
+        device_sink([(k, v.view(rows, cols)) for k, v in res.items()])
+        return {}
     return {k: v.cpu().numpy().reshape(rows, cols) for k, v in res.items()}
 
 
 def trendline_rasters_device(engine, planes, scene, dates, shape, dest=None,
                              template_dtype=np.int16, mode='reference', attrs=TRENDLINE_ATTRS,
-                             sink=None):
+                             sink=None, device_sink=None):
     """trendline_rasters for [Y, P] planes in device memory: the winning acquisition dates come
     from lt_winner_presence, each 'trendline/<date>-<attr>' raster from lt_raster_assemble, one
     year slot at a time; sink(key, array) receives each raster as it reaches the host (default:
-    collected into the returned dict). Dates shared by two observations fall back to the host."""
+    collected into the returned dict). device_sink: when given, each date's assembled rasters go
+    to device_sink([(key, [rows, cols] device tensor), ...]) in one batch instead and nothing is
+    copied down here. Dates shared by two observations fall back to the host."""
     import ctypes
     import torch
     from .index_eqn import DTYPES
@@ -364,6 +455,9 @@ def trendline_rasters_device(engine, planes, scene, dates, shape, dest=None,
             jobs.append(j)
             outs.append(('trendline/%s-%s' % (names[o], a), out))
         engine.raster_assemble(jobs)
+        if device_sink is not None:
+            device_sink([(key, out.view(rows, cols)) for key, out in outs])
+            continue
         for key, out in outs:
             arr = out.cpu().numpy().reshape(rows, cols)
             if sink is not None:

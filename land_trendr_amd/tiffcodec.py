@@ -23,7 +23,8 @@ def _lib():
         if not os.path.exists(LIB_PATH):
             raise RuntimeError('%s not built: run __graft_entry__.build()' % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
-        for f in (L.lt_lzw_decode, L.lt_lzw_encode, L.lt_lzw_decode_core):
+        for f in (L.lt_lzw_decode, L.lt_lzw_encode, L.lt_lzw_decode_core,
+                  L.lt_lzw_encode_core):
             f.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64]
             f.restype = ctypes.c_int64
         i64, vp, ci = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
@@ -61,6 +62,19 @@ def lzw_encode(raw):
     cap = len(raw) * 3 // 2 + 16
     out = np.empty(cap, np.uint8)
     n = _lib().lt_lzw_encode(raw, len(raw), out.ctypes.data, cap)
+    if n < 0:
+        raise ValueError('LZW: encode failed (%d)' % n)
+    return out[:n].tobytes()
+
+
+def lzw_encode_core(raw, cap=None):
+    """lzw_encode by the encoder core the device runs (lt_lzw_core.h, host build): the same
+    bytes. cap: the output space offered (default: the worst case)."""
+    raw = bytes(raw)
+    if cap is None:
+        cap = len(raw) * 3 // 2 + 16
+    out = np.empty(max(cap, 1), np.uint8)
+    n = _lib().lt_lzw_encode_core(raw, len(raw), out.ctypes.data, cap)
     if n < 0:
         raise ValueError('LZW: encode failed (%d)' % n)
     return out[:n].tobytes()

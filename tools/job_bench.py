@@ -14,7 +14,7 @@ would, on cuda:0, and the script prints one JSON line:
     compared with every output plane (the oracle is the checker here, never a producer).
 
     python tools/job_bench.py --rows 7000 --cols 7000 --years 30 [--trendline] [--check 20000]
-                              [--decode {host,device}]
+                              [--decode {host,device}] [--encode {host,device}]
 """
 import argparse
 import json
@@ -158,6 +158,9 @@ def main():
     ap.add_argument('--decode', default='host', choices=('host', 'device'),
                     help="where the rasters' strips are decoded (LocalJob decode=): liblt_io.so on "
                          'the host threads, or the HIP strip decoder on the GPU')
+    ap.add_argument('--encode', default='host', choices=('host', 'device'),
+                    help="where the output rasters' strips are encoded (LocalJob encode=): "
+                         'liblt_io.so on the host threads, or the HIP strip encoder on the GPU')
     a = ap.parse_args()
     import torch
     from land_trendr_amd.ingest import host_threads
@@ -170,7 +173,7 @@ def main():
               flush=True)
         P = a.rows * a.cols
         j = LocalJob(a.work, 'bench', device=0, tile_pixels=a.tile, trendline=a.trendline,
-                     on_error='skip', decode=a.decode)
+                     on_error='skip', decode=a.decode, encode=a.encode)
         t = {}
         files = None
         for step in ('setup', 'parse', 'analyze', 'output'):
@@ -215,6 +218,7 @@ def main():
                'analyze_parts_s': {k: round(v, 3) for k, v in getattr(j, 'analyze_s', {}).items()},
                'upload': os.environ.get('LT_JOB_UPLOAD', 'whole'),
                'decode': a.decode, 'decode_stats': j.decode_stats,
+               'encode': a.encode, 'encode_stats': j.encode_stats,
                'decode_times_s': {k: round(v, 3)
                                   for k, v in getattr(j, 'decode_times', {}).items()}}
         if a.diag:
