@@ -386,6 +386,42 @@ typedef struct {
  * Compression 1 is one coalesced kernel straight into `out`. */
 int lt_tiff_encode_strips_dev(lt_ctx* ctx, const lt_encode_job* jobs, int n_jobs, void* stream);
 
+/* ---- ingest: rasters sampled at the grid points on the device (an added export of ABI 8) ---------
+ * The reference samples every raster and every cloud mask at the template's grid points
+ * (pt2val, utils.py:285-297; apply_grid, utils.py:328-359). In the job's raster
+ * order grid pixel p = r * grid_w + c has the coordinates (x of column c, y of row r), so the
+ * source column depends on c alone and the source row on r alone: the caller computes the two
+ * offset axes on the host (ingest.axis_offsets: numpy's negative-index wrap applied, -1 where
+ * pt2val raises) and the device does the integer gather. */
+enum { LT_SAMPLE_BANDS = 0, LT_SAMPLE_MASK = 1 };
+typedef struct {
+  const void* src;            /* DEVICE [src_bands][src_h][src_w], native byte order        */
+  int32_t bps, src_bands;     /* bytes per sample: 1, 2, 4, 8                               */
+  int64_t src_h, src_w;
+  const int32_t* xoff;        /* DEVICE [grid_w]: source column of grid column c, -1 = off  */
+  const int32_t* yoff;        /* DEVICE [grid_h]: source row of grid row r, -1 = off        */
+  int64_t grid_w, grid_h;
+  int64_t p0, n;              /* grid pixels p0 .. p0+n-1, p = r * grid_w + c               */
+  int32_t n_sel, sel[16];     /* source band of output plane b (MASK: sel[0] only)          */
+  void* out; int64_t out_stride; /* plane b at out + b*out_stride samples; pixel p0+i at i  */
+  uint8_t* valid;             /* DEVICE [n]                                                 */
+  int32_t mode;
+} lt_sample_job;
+/* n_jobs sampling jobs, in order and asynchronous on `stream`. With on = xoff[c] >= 0 &&
+ * yoff[r] >= 0 for pixel i of a job:
+ *   LT_SAMPLE_BANDS  out[b][i] = on ? src[sel[b]][yoff[r] * src_w + xoff[c]] : 0 (a 64-bit index),
+ *                    valid[i] = on: what np.take at grid_offsets' indices, zero where pt2val
+ *                    raises, gives per band (ingest.ingest_stack);
+ *   LT_SAMPLE_MASK   valid[i] &= !(on && every byte of the sample of band sel[0] is zero): a grid
+ *                    point whose mask value is 0 is skipped (utils.py:351-356); `out` is unused.
+ * LT_ERR_ARG, with nothing launched, for a bps other than 1, 2, 4, 8, a bad mode, n_sel outside
+ * 1..16, a sel outside the source's bands, a negative size (out_stride < n in BANDS mode), sizes of
+ * 2^31 or more, p0 + n > grid_w * grid_h, a null pointer of a job with n > 0, and src or out not
+ * aligned to bps. Offsets at or past src_w / src_h are the caller's to exclude; the kernel treats
+ * them as off the raster and never reads outside `src`. The per-pixel logic is
+ * land_trendr_amd/csrc/lt_sample.h, the source liblt_io.so's lt_grid_sample is compiled from. */
+int lt_grid_sample_dev(lt_ctx* ctx, const lt_sample_job* jobs, int n_jobs, void* stream);
+
 /* Stage timing: when enabled, each lt_analyze_tile brackets its kernels with hipEvents on the
  * launch stream; lt_ctx_stage_ms returns the accumulated milliseconds per stage
  * (0 = analyze: every pixel with the lazy DP, 1 = resolve: the deferred pixels with the exact-OPT

@@ -53,6 +53,19 @@ int64_t lt_tiff_encode_strips(const uint8_t* in, int bands, int64_t rows, int64_
                               int64_t rows_per_strip, int compression, int predictor, uint8_t* out,
                               int64_t cap, int64_t* strip_sizes, int threads);
 
+/* One raster sampled at the grid points of a job in raster order: what pt2val / apply_grid do per
+ * point (utils.py:285-297, 328-359 of the reference), by the sampling core the device runs
+ * (land_trendr_amd/csrc/lt_sample.h; lt_grid_sample_dev of include/lt_abi.h, whose lt_sample_job
+ * these arguments spell out, every pointer a host pointer) on `threads` threads. mode 0 (bands):
+ * out[b][i] = on ? src[sel[b]][yoff[r] * src_w + xoff[c]] : 0 and valid[i] = on for grid pixel
+ * p0 + i = r * grid_w + c, on = both offsets inside the source; mode 1 (mask): valid[i] &=
+ * !(on && the sample of band sel[0] is zero). Returns 0, or LT_IO_ERR_ARG (nothing written) for
+ * what lt_grid_sample_dev rejects. */
+int64_t lt_grid_sample(const void* src, int bps, int src_bands, int64_t src_h, int64_t src_w,
+                       const int32_t* xoff, const int32_t* yoff, int64_t grid_w, int64_t grid_h,
+                       int64_t p0, int64_t n, int n_sel, const int32_t* sel, void* out,
+                       int64_t out_stride, uint8_t* valid, int mode, int threads);
+
 #ifdef __cplusplus
 }
 #endif

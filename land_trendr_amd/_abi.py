@@ -167,6 +167,20 @@ class LtEncodeJob(ctypes.Structure):
                 ('strip_sizes', ctypes.c_void_p), ('total', ctypes.c_void_p)]
 
 
+LT_SAMPLE_BANDS, LT_SAMPLE_MASK = 0, 1
+
+
+class LtSampleJob(ctypes.Structure):
+    """lt_sample_job: one raster in device memory sampled at a range of grid pixels."""
+    _fields_ = [('src', ctypes.c_void_p), ('bps', ctypes.c_int32), ('src_bands', ctypes.c_int32),
+                ('src_h', ctypes.c_int64), ('src_w', ctypes.c_int64), ('xoff', ctypes.c_void_p),
+                ('yoff', ctypes.c_void_p), ('grid_w', ctypes.c_int64), ('grid_h', ctypes.c_int64),
+                ('p0', ctypes.c_int64), ('n', ctypes.c_int64), ('n_sel', ctypes.c_int32),
+                ('sel', ctypes.c_int32 * 16), ('out', ctypes.c_void_p),
+                ('out_stride', ctypes.c_int64), ('valid', ctypes.c_void_p),
+                ('mode', ctypes.c_int32)]
+
+
 class LtIndexIO(ctypes.Structure):
     _fields_ = [('n_pix', ctypes.c_int64), ('n_obs', ctypes.c_int64),
                 ('obs_stride', ctypes.c_int64), ('band_stride', ctypes.c_int64),
@@ -204,7 +218,7 @@ EXPORTS = ['lt_abi_version', 'lt_ctx_create', 'lt_ctx_destroy', 'lt_last_error',
            'lt_settings_compile', 'lt_raster_assemble', 'lt_winner_presence',
            'lt_index_linearize', 'lt_ctx_set_jit_mode', 'lt_jit_prepare', 'lt_ctx_jit_stats',
            'lt_jit_source', 'lt_analyze_tiles_ev', 'lt_tiff_decode_strips_dev',
-           'lt_tiff_encode_strips_dev']
+           'lt_tiff_encode_strips_dev', 'lt_grid_sample_dev']
 
 LT_JIT_SYNC, LT_JIT_ASYNC = 0, 1
 LT_JIT_SRC_SPEC, LT_JIT_SRC_SCENE, LT_JIT_SRC_FIELDS = 1, 2, 4
@@ -283,6 +297,7 @@ def load_lib(path=None):
     lib.lt_jit_source.restype = ctypes.c_int
     lib.lt_tiff_decode_strips_dev.argtypes = [vp, ctypes.POINTER(LtStripsJob), ctypes.c_int, vp]
     lib.lt_tiff_encode_strips_dev.argtypes = [vp, ctypes.POINTER(LtEncodeJob), ctypes.c_int, vp]
+    lib.lt_grid_sample_dev.argtypes = [vp, ctypes.POINTER(LtSampleJob), ctypes.c_int, vp]
     if lib.lt_abi_version() != LT_ABI_VERSION:
         raise RuntimeError('liblt_hip.so ABI %d != %d' % (lib.lt_abi_version(), LT_ABI_VERSION))
     if path is None:

@@ -17,6 +17,7 @@
 
 #include "../../include/lt_io.h"
 #include "lt_lzw_core.h"
+#include "lt_sample.h"
 
 namespace {
 
@@ -428,6 +429,42 @@ int64_t lt_lzw_decode_core(const uint8_t* in, int64_t n_in, uint8_t* out, int64_
 int64_t lt_lzw_encode_core(const uint8_t* in, int64_t n_in, uint8_t* out, int64_t cap) {
   uint32_t table[lt_lzw::kEncSlots];
   return lt_lzw::encode(in, n_in, out, cap, lt_lzw::FlatTable{table});
+}
+
+// The sampling core the device runs (lt_sample.h, lt_sample.hip), compiled for the host: the
+// job's groups of pixels in chunks over the pool.
+int64_t lt_grid_sample(const void* src, int bps, int src_bands, int64_t src_h, int64_t src_w,
+                       const int32_t* xoff, const int32_t* yoff, int64_t grid_w, int64_t grid_h,
+                       int64_t p0, int64_t n, int n_sel, const int32_t* sel, void* out,
+                       int64_t out_stride, uint8_t* valid, int mode, int threads) {
+  lt_sample::Args a;
+  a.src = src;
+  a.bps = bps;
+  a.src_bands = src_bands;
+  a.src_h = src_h;
+  a.src_w = src_w;
+  a.xoff = xoff;
+  a.yoff = yoff;
+  a.grid_w = grid_w;
+  a.grid_h = grid_h;
+  a.p0 = p0;
+  a.n = n;
+  a.n_sel = n_sel;
+  for (int b = 0; b < lt_sample::kMaxSel; b++)  // (a null sel, or a bad n_sel: rejected below)
+    a.sel[b] = !sel ? -1 : (n_sel <= lt_sample::kMaxSel && b < n_sel ? sel[b] : 0);
+  a.out = out;
+  a.out_stride = out_stride;
+  a.valid = valid;
+  a.mode = mode;
+  if (lt_sample::check(a)) return LT_IO_ERR_ARG;
+  constexpr int64_t kChunk = 4096;  // groups per work item
+  const int64_t n_groups = lt_sample::groups(a);
+  pool_run((n_groups + kChunk - 1) / kChunk, threads, [&](int64_t k) -> int64_t {
+    const int64_t g1 = std::min(n_groups, (k + 1) * kChunk);
+    for (int64_t g = k * kChunk; g < g1; g++) lt_sample::sample_group_of(a, g);
+    return 0;
+  });
+  return 0;
 }
 
 }  // extern "C"

@@ -47,6 +47,7 @@ class Engine:
         self.ctx = ctx
         self._decode_lock = threading.Lock()
         self._encode_lock = threading.Lock()
+        self._sample_lock = threading.Lock()
 
     def close(self):
         if self.ctx:
@@ -412,6 +413,99 @@ class Engine:
                                                            ctypes.c_void_p(st.cuda_stream)),
                         'lt_tiff_encode_strips_dev')
         return res
+
+    # --- ingest: rasters sampled at the grid points on the device (lt_grid_sample_dev) ---
+    def sample_grid(self, jobs, stream=None):
+        """Rasters in device memory sampled at ranges of a raster-order grid by the HIP sampling
+        kernel (lt_sample.hip), the jobs of one call in order: what ingest_stack's np.take at
+        grid_offsets' indices, the zeroing off the raster and the mask rule give. A job is a dict:
+          src       contiguous device tensor [bands, rows, cols] (1, 2, 4 or 8 byte samples);
+          xoff, yoff  the per-axis offsets (ingest.axis_offsets): host int32 arrays, checked
+                    against src's shape and uploaded here, or int32 device tensors [grid cols],
+                    [grid rows] (the caller's to have checked; the kernel reads nothing outside
+                    src either way);
+          p0, n     the grid pixels p0 .. p0 + n - 1 (pixel p: row p // cols, column p % cols);
+          mode      _abi.LT_SAMPLE_BANDS (default) or _abi.LT_SAMPLE_MASK;
+          sel       the source band of each output plane (default [0]; MASK reads sel[0]);
+          out       BANDS: device tensor [len(sel), >= n] of src's type, unit pixel stride: plane
+                    b gets band sel[b], zero off the raster;
+          valid     uint8 device tensor [>= n], unit stride: BANDS writes whether the pixel is on
+                    the raster, MASK clears it where the sample of band sel[0] is zero.
+        Raises LtError, with nothing launched, for what lt_grid_sample_dev rejects. Asynchronous
+        on `stream`; the caller keeps the tensors alive until it has run."""
+        import numpy as np
+        n_jobs = len(jobs)
+        arr = (_abi.LtSampleJob * max(n_jobs, 1))()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        keep = []
+
+        def bad(msg):
+            raise LtError('sample_grid: ' + msg)
+
+        for k, j in enumerate(jobs):
+            src = j['src']
+            if (not isinstance(src, torch.Tensor) or src.device != self.device or src.dim() != 3 or
+                    not src.is_contiguous() or src.is_complex() or
+                    src.element_size() not in (1, 2, 4, 8)):
+                bad('src must be a contiguous [bands, rows, cols] tensor of 1, 2, 4 or 8 byte '
+                    'samples on %s' % self.device)
+            nb, sh, sw = src.shape
+            mode = int(j.get('mode', _abi.LT_SAMPLE_BANDS))
+            if mode not in (_abi.LT_SAMPLE_BANDS, _abi.LT_SAMPLE_MASK):
+                bad('mode must be LT_SAMPLE_BANDS or LT_SAMPLE_MASK')
+            if mode == _abi.LT_SAMPLE_MASK and src.is_floating_point():
+                bad('floating-point masks are not taken (-0.0 == 0)')
+            sel = [int(b) for b in j.get('sel', [0])]
+            if not 1 <= len(sel) <= 16 or any(not 0 <= b < nb for b in sel):
+                bad('sel must name 1..16 of the source\'s %d bands' % nb)
+            p0, n = int(j['p0']), int(j['n'])
+            offs = []
+            for name, lim in (('xoff', sw), ('yoff', sh)):
+                o = j[name]
+                if isinstance(o, torch.Tensor):
+                    if (o.dtype != torch.int32 or o.dim() != 1 or not o.is_contiguous() or
+                            o.device != self.device):
+                        bad('%s must be a contiguous int32 tensor on %s' % (name, self.device))
+                else:
+                    h = np.asarray(o)
+                    if h.dtype != np.int32 or h.ndim != 1:
+                        bad('%s must be a one-dimensional int32 array' % name)
+                    if h.size and (int(h.min()) < -1 or int(h.max()) >= lim):
+                        bad('%s outside the source raster' % name)
+                    with torch.cuda.stream(st):
+                        o = torch.from_numpy(np.ascontiguousarray(h)).to(self.device)
+                    keep.append(o)
+                offs.append(o)
+            gw, gh = offs[0].numel(), offs[1].numel()
+            if p0 < 0 or n < 0 or p0 + n > gw * gh:
+                bad('p0 + n outside the grid of %d x %d' % (gh, gw))
+            valid = j['valid']
+            if (not isinstance(valid, torch.Tensor) or valid.dtype != torch.uint8 or
+                    valid.dim() != 1 or valid.device != self.device or valid.numel() < n or
+                    (valid.numel() > 1 and valid.stride(0) != 1)):
+                bad('valid must be a uint8 [>= n] tensor with unit stride on %s' % self.device)
+            a = arr[k]
+            out = j.get('out')
+            if mode == _abi.LT_SAMPLE_BANDS:
+                if (not isinstance(out, torch.Tensor) or out.dtype != src.dtype or
+                        out.device != self.device or out.dim() != 2 or
+                        out.shape[0] != len(sel) or out.shape[1] < n or
+                        (out.shape[1] > 1 and out.stride(1) != 1) or
+                        (len(sel) > 1 and out.stride(0) < n)):
+                    bad('out must be a %s [%d, >= n] tensor with unit pixel stride on %s'
+                        % (src.dtype, len(sel), self.device))
+                a.out = out.data_ptr()
+                a.out_stride = out.stride(0) if len(sel) > 1 else max(n, out.stride(0))
+            a.src, a.bps, a.src_bands, a.src_h, a.src_w = src.data_ptr(), src.element_size(), nb, sh, sw
+            a.xoff, a.yoff, a.grid_w, a.grid_h = offs[0].data_ptr(), offs[1].data_ptr(), gw, gh
+            a.p0, a.n, a.n_sel = p0, n, len(sel)
+            for b, s in enumerate(sel):
+                a.sel[b] = s
+            a.valid, a.mode = valid.data_ptr(), mode
+        with self._sample_lock:  # one context: one caller at a time (its error text)
+            self._check(self.lib.lt_grid_sample_dev(self.ctx, arr, n_jobs,
+                                                    ctypes.c_void_p(st.cuda_stream)),
+                        'lt_grid_sample_dev')
 
     # --- JIT kernels of tiles carrying a program (lt_jit.h; lt_ctx_set_jit_mode, lt_jit_prepare) ---
     def set_jit_mode(self, asynchronous):

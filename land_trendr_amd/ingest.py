@@ -213,6 +213,31 @@ def grid_offsets(gt, shape, lng, lat):
     return yo * cols + xo, ok
 
 
+def axis_offsets(gt, shape, xv, yv):
+    """grid_offsets per axis, for a grid whose point (r, c) has the coordinates (xv[c], yv[r])
+    (the job's raster order): pt2val's x offset depends on x alone and its y offset on y alone,
+    so len(xv) + len(yv) offsets stand for the whole grid. The same numpy operations as
+    grid_offsets, per axis: trunc((v - origin) * 1.0 / size), valid in [-n, n), negative offsets
+    wrapped by + n. Returns (xoff int32 [len(xv)], yoff int32 [len(yv)]): the raster column / row
+    of each grid column / row, -1 where pt2val raises; grid point (r, c) is sample
+    yoff[r] * cols + xoff[c] where both are >= 0 and off the raster otherwise. Rasters of 2^31 or
+    more rows or columns are not taken (ValueError)."""
+    rows, cols = shape
+    if rows >= 1 << 31 or cols >= 1 << 31:
+        raise ValueError('axis_offsets: rasters of 2^31 or more rows or columns are not taken')
+    top_left_x, pix_width, _, top_left_y, _, pix_height = gt
+
+    def axis(v, origin, size, n):
+        with np.errstate(all='ignore'):  # (a zero pixel size, inf or NaN coordinates: off)
+            o = np.trunc((np.asarray(v, np.float64) - origin) * 1.0 / size)
+            ok = (o >= -n) & (o < n)
+        o = np.where(ok, o, 0).astype(np.int64)
+        o = np.where(o < 0, o + n, o)
+        return np.where(ok, o, -1).astype(np.int32)
+
+    return axis(xv, top_left_x, pix_width, cols), axis(yv, top_left_y, pix_height, rows)
+
+
 def mask_name(rast_fn):
     """parse_mapper's mask key (mr_land_trendr_job.py:59): RAST_TRIGGER -> MASK_TRIGGER."""
     return rast_fn.replace(RAST_TRIGGER, MASK_TRIGGER)
@@ -293,7 +318,7 @@ class _Offsets:
 
 
 def ingest_stack(rast_fns, grid, mask_fns=None, bands=None, threads=None, pixels=None,
-                 raster_grid=None, on_raster=None, device_decode=None):
+                 raster_grid=None, on_raster=None, device_decode=None, device_sample=None):
     """parse_mapper over every analysis raster, as planes for analysis_reducer_batch.
 
     rast_fns: the (decompressed) analysis rasters, in the mapper order that becomes each pixel's
@@ -317,7 +342,13 @@ def ingest_stack(rast_fns, grid, mask_fns=None, bands=None, threads=None, pixels
     job's tiles back to back; what the host decodes in place); True: the callee has decoded it — into plane
     k of a device stack of its own (LocalJob decode='device') — so bands[k] is left unwritten here
     and on_raster gets None for bands_k; False: the host path, as without it. Masks are decoded
-    on the host either way."""
+    on the host either way.
+    device_sample(k, ds, mask ds or None) -> bool: with raster_grid, offered every raster k (its
+    open GeoTiff and its mask's) before the paths above, whatever its extent, band count and the
+    pixel ranges; True: the callee has sampled the raster and its mask at the gathered grid points
+    into plane k and validity row k of a device stack of its own (LocalJob sample='device'), so
+    neither bands[k] nor valid[k] is written here and on_raster gets None for both; False: the
+    paths above, as without it."""
     from concurrent.futures import ThreadPoolExecutor
     lng, lat = grid if isinstance(grid, tuple) else grid_points(grid)
     P = len(lng)
@@ -376,6 +407,12 @@ def ingest_stack(rast_fns, grid, mask_fns=None, bands=None, threads=None, pixels
         if max(numbers) > ds.bands:
             raise Exception('Band %s requested but raster only has %s bands' % (max(numbers),
                                                                                  ds.bands))
+        if device_sample is not None and raster_grid is not None:
+            mds = _open(mask_fns[k]) if mask_fns[k] else None
+            if device_sample(k, ds, mds):  # bands, extent and mask: all on the device
+                if on_raster is not None:
+                    on_raster(k, None, None)
+                return filename2date(fn)
         idx, ok, ident = offsets(ds)
         whole = (ident and idx is None and sel == list(range(ds.bands)) and
                  ds.width * ds.height == P)  # raster order, every band

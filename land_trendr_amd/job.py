@@ -52,25 +52,32 @@ OUT_RASTS = '%s/output/rasters/'
 class _LazyBands(dict):
     """An ingest_stack result whose 'bands' array is completed on first access (LocalJob
     decode='device': the planes of the rasters decoded on the GPU come down from the device
-    stack then; the job itself never asks)."""
+    stack then; the job itself never asks), and, with fill_valid, its 'valid' array the same way
+    (sample='device': the validity rows of the rasters sampled on the GPU)."""
 
-    def __init__(self, stack, fill):
+    def __init__(self, stack, fill, fill_valid=None):
         super().__init__(stack)
         self._fill = fill
+        self._fill_valid = fill_valid
 
-    def _complete(self):
-        fill, self._fill = self._fill, None
-        if fill is not None:
-            fill(dict.__getitem__(self, 'bands'))
+    def _complete(self, key=None):
+        if key in (None, 'bands'):
+            fill, self._fill = self._fill, None
+            if fill is not None:
+                fill(dict.__getitem__(self, 'bands'))
+        if key in (None, 'valid'):
+            fill, self._fill_valid = self._fill_valid, None
+            if fill is not None:
+                fill(dict.__getitem__(self, 'valid'))
 
     def __getitem__(self, key):
-        if key == 'bands':
-            self._complete()
+        if key in ('bands', 'valid'):
+            self._complete(key)
         return dict.__getitem__(self, key)
 
     def get(self, key, default=None):
-        if key == 'bands':
-            self._complete()
+        if key in ('bands', 'valid'):
+            self._complete(key)
         return dict.get(self, key, default)
 
     def items(self):
@@ -85,7 +92,7 @@ class _LazyBands(dict):
 class LocalJob:
     def __init__(self, root, job, device=None, tile_pixels=1 << 22, trendline=True,
                  raster_mode='reference', pre_threshold_mode='reference', on_error='raise',
-                 work_dir=None, engine=None, decode=None, encode=None):
+                 work_dir=None, engine=None, decode=None, encode=None, sample=None):
         """engine: the analysis engine (default: engine.get_engine of `device`, the HIP library);
         tests pass a CPU double (tests/engine_double.py) to run the multi-rank path over gloo.
         decode: 'host' (default; LT_JOB_DECODE overrides the default) — every raster's strips are
@@ -97,7 +104,16 @@ class LocalJob:
         raster's strips with liblt_io.so on the host threads; 'device' — where output() assembles
         the rasters on the GPU, the HIP strip encoder (Engine.encode_strips) encodes each assembled
         batch there and only the strips come down; elsewhere (a CPU engine, host assembly) the
-        host encoder as before; encode_stats counts the rasters by path."""
+        host encoder as before; encode_stats counts the rasters by path.
+        sample: 'host' (default; LT_JOB_SAMPLE overrides the default) — every raster that is not
+        the stack's planes as they are (another extent, spare bands, a rank's tiles of a
+        multi-rank job) and every cloud mask is gathered at the grid points on the host
+        (ingest.ingest_stack); 'device' (needs decode='device') — in raster order, a raster the
+        strip decoder takes is decoded into a scratch raster on the GPU and sampled there
+        (Engine.sample_grid) into its plane and validity row of the device stack, whatever its
+        extent and band count, and so is its mask (strip-organised, integer samples); the others
+        as with 'host'; sample_stats counts the rasters sampled on the device and the masks by
+        path."""
         if on_error not in ('raise', 'skip'):
             raise ValueError('on_error must be "raise" or "skip"')
         decode = decode or os.environ.get('LT_JOB_DECODE') or 'host'
@@ -110,9 +126,18 @@ class LocalJob:
             raise ValueError('encode must be "host" or "device"')
         self.encode = encode
         self.encode_stats = {'device': 0, 'host': 0}  # rasters by the path that encoded them
+        sample = sample or os.environ.get('LT_JOB_SAMPLE') or 'host'
+        if sample not in ('host', 'device'):
+            raise ValueError('sample must be "host" or "device"')
+        if sample == 'device' and decode != 'device':
+            raise ValueError('sample="device" needs decode="device"')
+        self.sample = sample
+        # rasters sampled on the device (Engine.sample_grid), cloud masks by where they were applied
+        self.sample_stats = {'rasters': 0, 'masks_device': 0, 'masks_host': 0}
         self.decode_times = {}  # device mode: thread-seconds of parse() inside the decoder
         self._stack_meta = None  # device mode: (sample type, [K, nb, Q]) of the device stack
         self._dev_keep = None    # device mode: the device stack behind stack['bands']
+        self._dev_keep_valid = None  # sample='device': its validity plane behind stack['valid']
         self.root, self.job, self.device = root, job, device
         self.tile_pixels = int(tile_pixels)
         self.trendline = trendline
@@ -130,6 +155,7 @@ class LocalJob:
         self._order = None       # grid point of each internal pixel (None: grid order)
         self._raster_hw = None   # (rows, cols) of the raster order, or None
         self.raster_grid = None  # (geotransform, rows, cols) of the raster order, or None
+        self._grid_axes = None   # (x of each grid column, y of each grid row) of the raster order
 
     @property
     def grid_fn(self):
@@ -238,6 +264,7 @@ class LocalJob:
             return  # some point not on its own pixel: grid order, offsets per point
         self._raster_hw = (H, W)  # self.order: pixel (row r, column c) is grid point c * H + r
         self.grid_xy = (np.tile(xv, H), np.repeat(yv, W))
+        self._grid_axes = (xv, yv)  # grid point (r, c) is (xv[c], yv[r])
         self.raster_grid = (gt, H, W)
 
     def grid_wkts(self):
@@ -272,15 +299,19 @@ class LocalJob:
         # are decoded, on the worker that decoded them, while the other rasters decode: analyze()
         # then starts from the device stack
         self._dev_stack = None
-        self._stack_meta = self._dev_keep = None
+        self._stack_meta = self._dev_keep = self._dev_keep_valid = None
         self.decode_times = {}
         K, Q = len(self.rast_fns), sum(t.n for t in self.mosaic.mine)
         up = self._stack_uploader(K, len(eqn_bands), Q)
-        dec = self._device_decoder(up, K, len(eqn_bands), Q) if self.decode == 'device' else None
+        dec = (self._device_decoder(up, K, len(eqn_bands), Q, eqn_bands)
+               if self.decode == 'device' else None)
+        # sample='device': in raster order the decoder is offered every raster first, with its mask
+        smp = dec.sample if (dec is not None and self.sample == 'device' and
+                             self.raster_grid is not None) else None
         self.stack = ingest_stack(self.rast_fns, self.grid_xy, self.mask_fns, bands=eqn_bands,
                                   pixels=[(t.p0, t.p1) for t in self.mosaic.mine],
                                   raster_grid=self.raster_grid, on_raster=up,
-                                  device_decode=dec)
+                                  device_decode=dec, device_sample=smp)
         t_sync = time.perf_counter()
         if up is not None and up.bands is not None:
             import torch
@@ -288,16 +319,24 @@ class LocalJob:
             self._dev_stack = (up.bands, up.valid)
         if dec is not None:  # where a device-decode parse spent its time (thread-seconds)
             self.decode_times = dict(dec.times, sync=time.perf_counter() - t_sync)
-        self.decode_stats = {'device': len(dec.taken) if dec is not None else 0,
-                             'host': K - (len(dec.taken) if dec is not None else 0)}
+        on_dev = (dec.taken | dec.sampled) if dec is not None else set()
+        self.decode_stats = {'device': len(on_dev), 'host': K - len(on_dev)}
+        n_masks = sum(1 for m in self.mask_fns if m)
+        self.sample_stats = {'rasters': len(dec.sampled) if dec is not None else 0,
+                             'masks_device': dec.masks if dec is not None else 0,
+                             'masks_host': n_masks - (dec.masks if dec is not None else 0)}
         if dec is not None:
             dec.check()
-            if dec.taken:
-                # the job reads the device stack from here on; stack['bands'] stays usable for
-                # callers: the rasters decoded on the device come down on first access
-                self._stack_meta = (self.stack['bands'].dtype, tuple(self.stack['bands'].shape))
+            if on_dev:
+                # the job reads the device stack from here on; stack['bands'] and stack['valid']
+                # stay usable for callers: the planes of the rasters decoded on the device, and the
+                # validity rows of those sampled there, come down on first access
+                hb = dict.__getitem__(self.stack, 'bands')
+                self._stack_meta = (hb.dtype, tuple(hb.shape))
                 self._dev_keep = up.bands
-                self.stack = _LazyBands(self.stack, self._fill_bands(sorted(dec.taken)))
+                self._dev_keep_valid = up.valid if dec.sampled else None
+                self.stack = _LazyBands(self.stack, self._fill_bands(sorted(on_dev)),
+                                        self._fill_valid(sorted(dec.sampled)))
         return self.stack
 
     def _fill_bands(self, taken):
@@ -307,7 +346,14 @@ class LocalJob:
                 host[k] = dev[k].cpu().numpy()
         return fill
 
-    def _device_decoder(self, up, K, nb, Q):
+    def _fill_valid(self, sampled):
+        def fill(host):
+            dev, self._dev_keep_valid = self._dev_keep_valid, None
+            for k in sampled:
+                host[k] = dev[k].cpu().numpy()
+        return fill if sampled else None
+
+    def _device_decoder(self, up, K, nb, Q, eqn_bands=None):
         """ingest_stack's device_decode of a decode='device' job (None: host decode for the whole
         job — no GPU uploader, or a stack above the 64 GB rule analyze() applies for the whole-stack
         upload). Makes the [K, nb, Q] device stack up front in the first raster's sample type;
@@ -333,24 +379,33 @@ class LocalJob:
             streams = [torch.cuda.Stream(device=up.device) for _ in range(8)]
         tl = threading.local()
         lock = threading.Lock()
-        rast_fns = self.rast_fns
+        rast_fns, mask_fns = self.rast_fns, self.mask_fns
+        # sample='device': the stack's pixel ranges (p0, p1, column of p0), the bands gathered, the
+        # grid's axes, and the per-axis offsets on the device per (geotransform, rows, cols)
+        spans, q = [], 0
+        for t in self.mosaic.mine:
+            spans.append((t.p0, t.p1, q))
+            q += t.n
+        sel = [b - 1 for b in (eqn_bands or [])]
+        axes = getattr(self, '_grid_axes', None) if self.raster_grid is not None else None
+        offsets = {}
 
         class Dec:
             def __init__(self):
                 self.taken, self.errs, self.threads = set(), [], 0
+                self.sampled, self.masks = set(), 0
                 # seconds summed over the worker threads: waiting for the staging buffer,
                 # allocating it, and GeoTiff.read_device (staging copy, H2D and launch calls)
                 self.times = {'wait': 0.0, 'alloc': 0.0, 'read': 0.0}
 
-            def __call__(self, k, ds):
-                if (not ds.device_eligible() or ds.bands != nb or
-                        ds.dtype.newbyteorder('=') != dtype or ds.width * ds.height != Q):
-                    return False
+            def _read(self, ds, out):
+                """ds decoded into `out` on this worker's stream, through its staging buffer;
+                returns the error word and the seconds spent (wait, alloc, read)."""
                 if not hasattr(tl, 'stream'):
                     with lock:
                         tl.stream = streams[self.threads % len(streams)]
                         self.threads += 1
-                    tl.staging, tl.staged = None, None
+                    tl.staging, tl.staged, tl.scratch = None, None, None
                 need = len(ds._d) + 16 * len(ds.tags[273]) + 16
                 t0 = time.perf_counter()
                 if tl.staged is not None:  # the previous raster's bytes have left the buffer
@@ -359,25 +414,85 @@ class LocalJob:
                 if tl.staging is None or tl.staging.numel() < need:
                     tl.staging = torch.empty(need, dtype=torch.uint8, pin_memory=True)
                 t2 = time.perf_counter()
-                out = up.bands[k].view(ds.bands, ds.height, ds.width)
+                if out is None:  # the worker's scratch raster, grown on demand
+                    n = ds.bands * ds.height * ds.width * ds.dtype.itemsize
+                    if tl.scratch is None or tl.scratch.numel() < n:
+                        with torch.cuda.stream(tl.stream):
+                            tl.scratch = None
+                            tl.scratch = torch.empty(n, dtype=torch.uint8, device=up.device)
+                    tdt = torch.from_numpy(np.empty(0, ds.dtype.newbyteorder('='))).dtype
+                    out = tl.scratch[:n].view(tdt).view(ds.bands, ds.height, ds.width)
                 _, err = ds.read_device(eng, out=out, stream=tl.stream, check=False,
                                         staging=tl.staging)
                 t3 = time.perf_counter()
                 tl.staged = ds.staged
+                return out, err, (t1 - t0, t2 - t1, t3 - t2)
+
+            def _count(self, dts):
+                for key, dt in zip(('wait', 'alloc', 'read'), dts):
+                    self.times[key] += dt
+
+            def __call__(self, k, ds):
+                if (not ds.device_eligible() or ds.bands != nb or
+                        ds.dtype.newbyteorder('=') != dtype or ds.width * ds.height != Q):
+                    return False
+                _, err, dts = self._read(ds, up.bands[k].view(ds.bands, ds.height, ds.width))
                 with lock:
                     self.taken.add(k)
-                    self.errs.append((k, err))
-                    for key, dt in (('wait', t1 - t0), ('alloc', t2 - t1), ('read', t3 - t2)):
-                        self.times[key] += dt
+                    self.errs.append((k, rast_fns[k], err))
+                    self._count(dts)
+                return True
+
+            def _offsets(self, ds):
+                from .ingest import axis_offsets
+                key = (ds.geotransform(), ds.height, ds.width)
+                with lock:
+                    hit = offsets.get(key)
+                    if hit is None:
+                        xo, yo = axis_offsets(key[0], (ds.height, ds.width), *axes)
+                        with torch.cuda.device(up.device):
+                            hit = offsets[key] = (torch.from_numpy(xo).to(up.device),
+                                                  torch.from_numpy(yo).to(up.device))
+                return hit
+
+            def sample(self, k, ds, mds):
+                """ingest_stack's device_sample: raster k and its mask decoded into this worker's
+                scratch raster and sampled at the stack's pixel ranges (Engine.sample_grid), all on
+                the worker's stream."""
+                if (axes is None or not sel or not ds.device_eligible() or
+                        ds.dtype.newbyteorder('=') != dtype or ds.bands < max(sel) + 1 or
+                        max(ds.height, ds.width) >= 1 << 31):
+                    return False
+                if mds is not None and not (mds.device_eligible() and mds.dtype.kind in 'iu' and
+                                            max(mds.height, mds.width) < 1 << 31):
+                    return False
+                for g, mode, name in ((ds, _abi.LT_SAMPLE_BANDS, rast_fns[k]),
+                                      (mds, _abi.LT_SAMPLE_MASK, mask_fns[k])):
+                    if g is None:
+                        continue
+                    xo, yo = self._offsets(g)
+                    src, err, dts = self._read(g, None)
+                    jobs = [dict(src=src, xoff=xo, yoff=yo, p0=p0, n=p1 - p0, mode=mode,
+                                 sel=sel if mode == _abi.LT_SAMPLE_BANDS else [0],
+                                 out=up.bands[k][:, q0:q0 + p1 - p0],
+                                 valid=up.valid[k][q0:q0 + p1 - p0])
+                            for p0, p1, q0 in spans]
+                    eng.sample_grid(jobs, stream=tl.stream)
+                    with lock:
+                        self.errs.append((k, name, err))
+                        self._count(dts)
+                with lock:
+                    self.sampled.add(k)
+                    self.masks += mds is not None
                 return True
 
             def check(self):
                 from .geotiff import TiffError
-                for k, err in sorted(self.errs, key=lambda e: e[0]):
+                for _, name, err in sorted(self.errs, key=lambda e: e[:2]):
                     rc = int(err.item())
                     if rc != 0:
                         raise TiffError('%s: TIFF strips: corrupt or unsupported data (%d)'
-                                        % (rast_fns[k], rc))
+                                        % (name, rc))
         return Dec()
 
     def _stack_uploader(self, K, nb, Q):
@@ -406,7 +521,8 @@ class LocalJob:
                 with torch.cuda.device(dev):
                     if b is not None:  # (None: decoded on the device, already in plane k)
                         self.bands[k].copy_(torch.from_numpy(b))
-                    self.valid[k].copy_(torch.from_numpy(v))
+                    if v is not None:  # (None: sampled on the device, its validity row too)
+                        self.valid[k].copy_(torch.from_numpy(v))
         return Up()
 
     # 3. analysis_reducer, batched over pixel tiles: the mosaic path (runner.py) bench.py runs
@@ -459,10 +575,13 @@ class LocalJob:
         # device views of it; 'tile': each tile's bands gathered into a host copy first (a 2 GB
         # single-threaded copy per 16.8 Mpx tile, most of round 6's job analysis time)
         b_nbytes = int(np.prod(b_shape)) * np.dtype(b_dtype).itemsize
+        # (device mode: the [K, Q] uint8 validity plane's size from the stack's shape as well; its
+        # device-sampled rows are only filled when a caller reads stack['valid'])
+        v_nbytes = b_shape[0] * b_shape[2] if meta is not None else st['valid'].nbytes
         whole = (cuda and os.environ.get('LT_JOB_UPLOAD', 'whole') == 'whole' and
-                 (meta is not None or st['bands'].flags.c_contiguous) and
-                 st['valid'].flags.c_contiguous and
-                 b_nbytes + st['valid'].nbytes <= (64 << 30))
+                 (meta is not None or (st['bands'].flags.c_contiguous and
+                                       st['valid'].flags.c_contiguous)) and
+                 b_nbytes + v_nbytes <= (64 << 30))
         if whole:
             ds = getattr(self, '_dev_stack', None)
             if ds is not None and ds[0].device == dev and tuple(ds[0].shape) == tuple(b_shape):

@@ -33,6 +33,9 @@ def _lib():
         L.lt_tiff_decode_strips.restype = i64
         L.lt_tiff_encode_strips.argtypes = [vp, ci, i64, i64, ci, i64, ci, ci, vp, i64, vp, ci]
         L.lt_tiff_encode_strips.restype = i64
+        L.lt_grid_sample.argtypes = [vp, ci, ci, i64, i64, vp, vp, i64, i64, i64, i64, ci, vp, vp,
+                                     i64, vp, ci, ci]
+        L.lt_grid_sample.restype = i64
         _LIB = L
     return _LIB
 
@@ -183,6 +186,28 @@ def decode_strips(buf, offsets, counts, compression, predictor, dtype, big_endia
     if rc < 0:
         raise ValueError('TIFF strips: corrupt or unsupported data (%d)' % rc)
     return out
+
+
+def grid_sample(src, xoff, yoff, p0, n, sel, out, out_stride, valid, mode, threads=1):
+    """The sampling core the device runs (lt_sample.h), host build (liblt_io.so lt_grid_sample):
+    grid pixels p0 .. p0 + n - 1 of the grid len(yoff) x len(xoff) sampled from src, a C-contiguous
+    [bands, rows, cols] array, through the per-axis offsets (ingest.axis_offsets). mode 0: plane b
+    of `out` (a writable array whose first sample is plane 0's pixel p0, planes out_stride samples
+    apart; src's sample size) gets band sel[b], zero off the raster, and `valid` (uint8, n bytes)
+    whether the pixel is on it; mode 1: valid is cleared where the sample of band sel[0] is zero
+    (`out` may be None). ValueError for what the C side rejects."""
+    xoff = np.ascontiguousarray(xoff, np.int32)
+    yoff = np.ascontiguousarray(yoff, np.int32)
+    sel = np.ascontiguousarray(sel, np.int32)
+    if not src.flags.c_contiguous or src.ndim != 3:
+        raise ValueError('grid_sample: src must be a C-contiguous [bands, rows, cols] array')
+    rc = _lib().lt_grid_sample(src.ctypes.data, src.itemsize, src.shape[0], src.shape[1],
+                               src.shape[2], xoff.ctypes.data, yoff.ctypes.data, len(xoff),
+                               len(yoff), int(p0), int(n), len(sel), sel.ctypes.data,
+                               out.ctypes.data if out is not None else None, int(out_stride),
+                               valid.ctypes.data, int(mode), max(1, int(threads)))
+    if rc < 0:
+        raise ValueError('grid_sample: bad argument (%d)' % rc)
 
 
 def encode_strips(a, rows_per_strip, compression, predictor, threads):

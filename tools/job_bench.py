@@ -15,6 +15,7 @@ would, on cuda:0, and the script prints one JSON line:
 
     python tools/job_bench.py --rows 7000 --cols 7000 --years 30 [--trendline] [--check 20000]
                               [--decode {host,device}] [--encode {host,device}]
+                              [--sample {host,device}] [--shift N] [--mask PROB]
 """
 import argparse
 import json
@@ -34,10 +35,13 @@ SETTINGS = {'index_eqn': 'B1 - B2', 'line_cost': 10, 'target_date': '2014-07-01'
             'label_rules': [{'name': 'gd', 'val': 1, 'change_type': 'GD'}]}
 
 
-def make_stack(root, job, rows, cols, years, seed, mask_prob):
+def make_stack(root, job, rows, cols, years, seed, mask_prob, shift=0):
     """The job directory: one two-band int16 LZW GeoTIFF per acquisition date (raster order:
     pixel p of the scene at row p // cols, column p % cols) and, with mask_prob > 0, a cloudmask
-    raster per date. Returns (seconds, bytes written)."""
+    raster per date. shift = N > 0: every N-th raster is written with an extent of its own — its
+    origin a few pixels off the template's in both axes, a few rows and columns larger or smaller
+    (alternating), zeros outside the scene — and with two spare bands behind the two the index
+    reads, as a LEDAPS stack's dates differ. Returns (seconds, bytes written)."""
     import torch
     from land_trendr_amd.raster import write_geotiff
     from land_trendr_amd.synth import make_scene
@@ -55,7 +59,18 @@ def make_stack(root, job, rows, cols, years, seed, mask_prob):
         stem = 'LT5045029_%d_%03d_20120124_104859' % (d.year, d.timetuple().tm_yday)
         img = sc.bands[k].reshape(2, rows, cols).cpu().numpy()
         fn = os.path.join(rdir, stem + '_ledaps.tif')
-        write_geotiff(fn, img, geotransform=GT, nodata=None)
+        gt = GT
+        if shift > 0 and k % shift == shift - 1:
+            # raster pixel (y, x) is template pixel (y + sy, x + sx)
+            sgn = 1 if (k // shift) % 2 == 0 else -1
+            sx, sy, h, w = 3 * sgn, -2 * sgn, rows + 5 * sgn, cols - 4 * sgn
+            big = np.zeros((4, h, w), img.dtype)
+            y0, y1, x0, x1 = max(0, -sy), min(h, rows - sy), max(0, -sx), min(w, cols - sx)
+            big[:2, y0:y1, x0:x1] = img[:, y0 + sy:y1 + sy, x0 + sx:x1 + sx]
+            big[2:] = 7
+            img = big
+            gt = (GT[0] + sx * GT[1], GT[1], 0.0, GT[3] + sy * GT[5], 0.0, GT[5])
+        write_geotiff(fn, img, geotransform=gt, nodata=None)
         nbytes += os.path.getsize(fn)
         if sc.valid is not None:
             m = sc.valid[k].reshape(rows, cols).cpu().numpy()
@@ -158,6 +173,13 @@ def main():
     ap.add_argument('--decode', default='host', choices=('host', 'device'),
                     help="where the rasters' strips are decoded (LocalJob decode=): liblt_io.so on "
                          'the host threads, or the HIP strip decoder on the GPU')
+    ap.add_argument('--sample', default='host', choices=('host', 'device'),
+                    help='where rasters of another extent or band count and the cloud masks are '
+                         'sampled at the grid points (LocalJob sample=): numpy on the host, or the '
+                         'HIP sampling kernel on the GPU (needs --decode device)')
+    ap.add_argument('--shift', type=int, default=0,
+                    help='N > 0: every N-th raster gets an extent of its own (a few pixels off in '
+                         'both axes, a few rows and columns larger or smaller) and two spare bands')
     ap.add_argument('--encode', default='host', choices=('host', 'device'),
                     help="where the output rasters' strips are encoded (LocalJob encode=): "
                          'liblt_io.so on the host threads, or the HIP strip encoder on the GPU')
@@ -168,12 +190,13 @@ def main():
     shutil.rmtree(a.work, ignore_errors=True)
     os.makedirs(a.work)
     try:
-        gen_s, in_bytes = make_stack(a.work, 'bench', a.rows, a.cols, a.years, a.seed, a.mask)
+        gen_s, in_bytes = make_stack(a.work, 'bench', a.rows, a.cols, a.years, a.seed, a.mask,
+                                        a.shift)
         print('stack written: %.1f s, %.2f GB' % (gen_s, in_bytes / 1e9), file=sys.stderr,
               flush=True)
         P = a.rows * a.cols
         j = LocalJob(a.work, 'bench', device=0, tile_pixels=a.tile, trendline=a.trendline,
-                     on_error='skip', decode=a.decode, encode=a.encode)
+                     on_error='skip', decode=a.decode, encode=a.encode, sample=a.sample)
         t = {}
         files = None
         for step in ('setup', 'parse', 'analyze', 'output'):
@@ -218,6 +241,8 @@ def main():
                'analyze_parts_s': {k: round(v, 3) for k, v in getattr(j, 'analyze_s', {}).items()},
                'upload': os.environ.get('LT_JOB_UPLOAD', 'whole'),
                'decode': a.decode, 'decode_stats': j.decode_stats,
+               'sample': a.sample, 'shift': a.shift, 'mask': a.mask,
+               'sample_stats': j.sample_stats,
                'encode': a.encode, 'encode_stats': j.encode_stats,
                'decode_times_s': {k: round(v, 3)
                                   for k, v in getattr(j, 'decode_times', {}).items()}}
