@@ -97,7 +97,8 @@ typedef struct {
 
 /* Element types of raster planes (the GDAL band types a LandTrendr stack meets). */
 enum { LT_T_F64 = 0, LT_T_I16 = 1, LT_T_U16 = 2, LT_T_I32 = 3, LT_T_F32 = 4, LT_T_U8 = 5,
-       LT_T_U32 = 6, LT_T_I8 = 7, LT_T_I64 = 8 };
+       LT_T_U32 = 6, LT_T_I8 = 7, LT_T_I64 = 8,
+       LT_T_BOOL = 9 };     /* a mask program's comparison / boolean nodes; never a raster type  */
 /* An index_eqn program that is an integer linear form (lt_index_linearize): every arithmetic
  * node has the one integer type wrap_type, multiplications have a constant side, no division.
  * Its value for bands b[0..n_bands) is store_out(wrap(c0 + sum coef[s] * b[s])), the sum taken
@@ -158,7 +159,16 @@ enum { LT_OP_BAND = 1,      /* push band plane ival (0-based slot), in band_type
        LT_OP_ADD = 4, LT_OP_SUB = 5, LT_OP_MUL = 6,
        LT_OP_DIV = 7,       /* Python 2 '/': floor division on integer types, true on floats    */
        LT_OP_FLOORDIV = 8,  /* '//'                                                             */
-       LT_OP_NEG = 9 };
+       LT_OP_NEG = 9,
+       /* mask programs only (settings.json mask_eqn, lt_mask_*): rejected in an index program */
+       LT_OP_EQ = 10, LT_OP_NE = 11, LT_OP_LT = 12, LT_OP_LE = 13, LT_OP_GT = 14, LT_OP_GE = 15,
+                            /* compare: both operands cast to `type`, push a LT_T_BOOL; `type`  */
+                            /* LT_T_BOOL (EQ / NE only) compares two booleans                    */
+       LT_OP_AND = 16, LT_OP_OR = 17, LT_OP_XOR = 18, /* bitwise in an integer `type`, or of two */
+                            /* booleans (`type` LT_T_BOOL)                                       */
+       LT_OP_NOT = 19,      /* '~': bitwise in an integer `type`, logical on a boolean           */
+       LT_OP_SHL = 20, LT_OP_SHR = 21 }; /* shift the top of stack by the literal ival, which is */
+                            /* in [0, bits(type) - 1]; SHL wraps, SHR is arithmetic if signed    */
 /* One postfix operation. `type` is the numpy result type of the node (binary ops: both operands
  * are cast to it first, as numpy does); integer results wrap. */
 typedef struct {
@@ -190,6 +200,28 @@ typedef struct {
   void* out;
   int64_t band_pix_stride;
 } lt_index_io;
+
+/* ---- mask stage: settings.json mask_eqn (rast_algebra's mask_eqn, utils.py:447-484) ---------- */
+typedef struct lt_mask lt_mask;  /* a compiled mask_eqn program (lt_mask_compile) */
+/* A mask program is an lt_index_prog whose root is a LT_T_BOOL (out_type is ignored); a
+ * LT_OP_CONST_I of type LT_T_BOOL pushes the boolean ival != 0. n_bands counts the band planes of
+ * the stack it runs on; only the planes it names are read.
+ * Device buffers of one lt_mask_apply: band s of obs o, pixel p at bands[o*obs_stride +
+ * s*band_stride + p*band_pix_stride] (any non-negative strides, band_pix_stride >= 1); the
+ * validity byte of obs o, pixel p at valid[o*valid_stride + p], set to 0 where the program is
+ * false and never from 0 to non-zero. dropped (optional): the number of bytes turned from
+ * non-zero to 0 is added to *dropped. */
+typedef struct {
+  int64_t n_pix;
+  int64_t n_obs;
+  int64_t obs_stride;
+  int64_t band_stride;
+  int64_t band_pix_stride;
+  const void* bands;
+  uint8_t* valid;
+  int64_t valid_stride;       /* bytes between the validity rows of consecutive obs (>= n_pix) */
+  uint64_t* dropped;          /* device counter to add to, or NULL                             */
+} lt_mask_io;
 
 /* ---- settings.json compiled on the host (for non-Python hosts) -------------------------------- */
 /* The Python exception the reference raises for a rejected settings.json (lt_settings_compile). */
@@ -444,6 +476,17 @@ int lt_index_apply(lt_ctx* ctx, const lt_index* fn, const lt_index_io* io, void*
  * terms, mixed integer node types, a band type the kernel does not read, more than
  * LT_LIN_MAX_BANDS bands): such programs keep lt_index_apply. Host only, no context. */
 int lt_index_linearize(const lt_index_prog* prog, lt_index_lin* out);
+
+/* Mask stage (settings.json mask_eqn). lt_mask_codegen writes the HIP source generated for the
+ * mask program `prog` (host only; the length, or a negative LT_ERR_*). lt_mask_compile builds it
+ * with hiprtc for the context's device (cached per program inside the context, the handle freed
+ * with the context; LT_ERR_JIT with the compiler log in lt_last_error on failure). lt_mask_apply
+ * clears the validity bytes of the observations the program is false on, asynchronously on
+ * `stream`; LT_ERR_ARG (nothing launched) for null or negative arguments. The C settings compiler
+ * (lt_settings_compile) does not read mask_eqn: a non-Python host builds the program itself. */
+int lt_mask_codegen(const lt_index_prog* prog, char* buf, int64_t cap);
+int lt_mask_compile(lt_ctx* ctx, const lt_index_prog* prog, lt_mask** out);
+int lt_mask_apply(lt_ctx* ctx, const lt_mask* fn, const lt_mask_io* io, void* stream);
 
 /* ---- JIT kernels (lt_tile_in.index; ABI 7) -------------------------------------------------------
  * A tile carrying an index_eqn program runs analyze / resolve kernels compiled for it (hiprtc,

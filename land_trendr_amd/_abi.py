@@ -30,11 +30,14 @@ c_f64p = ctypes.POINTER(ctypes.c_double)
 
 # raster element types and the load-stage program (index_eqn)
 (LT_T_F64, LT_T_I16, LT_T_U16, LT_T_I32, LT_T_F32, LT_T_U8, LT_T_U32, LT_T_I8,
- LT_T_I64) = range(9)
+ LT_T_I64, LT_T_BOOL) = range(10)
 LT_MAX_PROG = 64
 LT_MAX_BANDS = 16
 (LT_OP_BAND, LT_OP_CONST_I, LT_OP_CONST_F, LT_OP_ADD, LT_OP_SUB, LT_OP_MUL, LT_OP_DIV,
  LT_OP_FLOORDIV, LT_OP_NEG) = range(1, 10)
+# mask programs only (settings.json mask_eqn)
+(LT_OP_EQ, LT_OP_NE, LT_OP_LT, LT_OP_LE, LT_OP_GT, LT_OP_GE, LT_OP_AND, LT_OP_OR, LT_OP_XOR,
+ LT_OP_NOT, LT_OP_SHL, LT_OP_SHR) = range(10, 22)
 
 
 class LtRule(ctypes.Structure):
@@ -188,6 +191,14 @@ class LtIndexIO(ctypes.Structure):
                 ('out', ctypes.c_void_p), ('band_pix_stride', ctypes.c_int64)]
 
 
+class LtMaskIO(ctypes.Structure):
+    _fields_ = [('n_pix', ctypes.c_int64), ('n_obs', ctypes.c_int64),
+                ('obs_stride', ctypes.c_int64), ('band_stride', ctypes.c_int64),
+                ('band_pix_stride', ctypes.c_int64), ('bands', ctypes.c_void_p),
+                ('valid', ctypes.c_void_p), ('valid_stride', ctypes.c_int64),
+                ('dropped', ctypes.c_void_p)]
+
+
 class LtTileOut(ctypes.Structure):
     _fields_ = [('stride', ctypes.c_int64), ('status', c_i32p), ('n_years', c_i32p),
                 ('winner', c_i16p), ('val_raw', c_f64p), ('val_fit', c_f64p), ('fit_m', c_f64p),
@@ -218,7 +229,8 @@ EXPORTS = ['lt_abi_version', 'lt_ctx_create', 'lt_ctx_destroy', 'lt_last_error',
            'lt_settings_compile', 'lt_raster_assemble', 'lt_winner_presence',
            'lt_index_linearize', 'lt_ctx_set_jit_mode', 'lt_jit_prepare', 'lt_ctx_jit_stats',
            'lt_jit_source', 'lt_analyze_tiles_ev', 'lt_tiff_decode_strips_dev',
-           'lt_tiff_encode_strips_dev', 'lt_grid_sample_dev']
+           'lt_tiff_encode_strips_dev', 'lt_grid_sample_dev', 'lt_mask_codegen',
+           'lt_mask_compile', 'lt_mask_apply']
 
 LT_JIT_SYNC, LT_JIT_ASYNC = 0, 1
 LT_JIT_SRC_SPEC, LT_JIT_SRC_SCENE, LT_JIT_SRC_FIELDS = 1, 2, 4
@@ -277,6 +289,10 @@ def load_lib(path=None):
     lib.lt_index_compile.argtypes = [vp, ctypes.POINTER(LtIndexProg), ctypes.POINTER(vp)]
     lib.lt_index_apply.argtypes = [vp, vp, ctypes.POINTER(LtIndexIO), vp]
     lib.lt_index_linearize.argtypes = [ctypes.POINTER(LtIndexProg), ctypes.POINTER(LtIndexLin)]
+    lib.lt_mask_codegen.argtypes = [ctypes.POINTER(LtIndexProg), ctypes.c_char_p, ctypes.c_int64]
+    lib.lt_mask_codegen.restype = ctypes.c_int
+    lib.lt_mask_compile.argtypes = [vp, ctypes.POINTER(LtIndexProg), ctypes.POINTER(vp)]
+    lib.lt_mask_apply.argtypes = [vp, vp, ctypes.POINTER(LtMaskIO), vp]
     lib.lt_raster_assemble.argtypes = [vp, ctypes.POINTER(LtRasterJob), ctypes.c_int, vp]
     lib.lt_winner_presence.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
                                        ctypes.c_int32, vp, vp]

@@ -19,6 +19,7 @@
 #include "lt_launch.h"
 #include "lt_pixel.h"
 #include "lt_index.h"
+#include "lt_mask.h"
 #include "lt_jit.h"
 #include "lt_kernels_dev.h"
 #include "lt_settings.h"
@@ -276,6 +277,7 @@ struct lt_ctx {
   bool set_used[kSets] = {};
   int last_set = 0, next_set = 0;
   std::map<std::string, lt_index*> index_fns;  // compiled load-stage kernels, by source
+  std::map<std::string, lt_mask*> mask_fns;    // compiled mask_eqn kernels, by source
   // JIT analyze / resolve kernels with an index_eqn program inlined (lt_jit.h), by spec_key
   std::map<uint64_t, JitEntry> jit;
   int jit_mode = LT_JIT_SYNC;
@@ -432,6 +434,10 @@ int lt_ctx_destroy(lt_ctx* c) {
   lt::decode_release(c->dec);
   lt::encode_release(c->enc);
   for (auto& kv : c->index_fns) {
+    if (kv.second->mod) (void)hipModuleUnload(kv.second->mod);
+    delete kv.second;
+  }
+  for (auto& kv : c->mask_fns) {
     if (kv.second->mod) (void)hipModuleUnload(kv.second->mod);
     delete kv.second;
   }
@@ -1279,25 +1285,16 @@ int lt_index_codegen(const lt_index_prog* prog, char* buf, int64_t cap) {
   return (int)src.size();
 }
 
-int lt_index_compile(lt_ctx* c, const lt_index_prog* prog, lt_index** out) {
-  if (!c) return LT_ERR_ARG;
-  if (!prog || !out) return fail(c, LT_ERR_ARG, "null argument%s");
-  *out = nullptr;
-  std::string err;
-  const std::string src = lt_idx::codegen(*prog, err);
-  if (src.empty()) return fail(c, LT_ERR_ARG, "%s", err.c_str());
-  auto it = c->index_fns.find(src);
-  if (it != c->index_fns.end()) {
-    *out = it->second;
-    return LT_OK;
-  }
+// A generated load-stage / mask source compiled with hiprtc for the context's device (no
+// fast-math: IEEE comparisons and divisions, no contraction).
+static int generated_compile(lt_ctx* c, const std::string& src, const char* name,
+                             std::vector<char>& code) {
   HIP_OR_FAIL(c, hipSetDevice(c->device));
   hipDeviceProp_t prop;
   HIP_OR_FAIL(c, hipGetDeviceProperties(&prop, c->device));
   const std::string arch = std::string("--offload-arch=") + prop.gcnArchName;
   hiprtcProgram rp;
-  if (hiprtcCreateProgram(&rp, src.c_str(), "lt_index.hip", 0, nullptr, nullptr) !=
-      HIPRTC_SUCCESS)
+  if (hiprtcCreateProgram(&rp, src.c_str(), name, 0, nullptr, nullptr) != HIPRTC_SUCCESS)
     return fail(c, LT_ERR_JIT, "hiprtcCreateProgram failed%s");
   const char* opts[] = {arch.c_str(), "-O3", "-ffp-contract=off"};
   const hiprtcResult rc = hiprtcCompileProgram(rp, 3, opts);
@@ -1311,9 +1308,27 @@ int lt_index_compile(lt_ctx* c, const lt_index_prog* prog, lt_index** out) {
   }
   size_t code_size = 0;
   hiprtcGetCodeSize(rp, &code_size);
-  std::vector<char> code(code_size);
+  code.resize(code_size);
   hiprtcGetCode(rp, code.data());
   hiprtcDestroyProgram(&rp);
+  return LT_OK;
+}
+
+int lt_index_compile(lt_ctx* c, const lt_index_prog* prog, lt_index** out) {
+  if (!c) return LT_ERR_ARG;
+  if (!prog || !out) return fail(c, LT_ERR_ARG, "null argument%s");
+  *out = nullptr;
+  std::string err;
+  const std::string src = lt_idx::codegen(*prog, err);
+  if (src.empty()) return fail(c, LT_ERR_ARG, "%s", err.c_str());
+  auto it = c->index_fns.find(src);
+  if (it != c->index_fns.end()) {
+    *out = it->second;
+    return LT_OK;
+  }
+  std::vector<char> code;
+  const int rc = generated_compile(c, src, "lt_index.hip", code);
+  if (rc != LT_OK) return rc;
   lt_index* f = new lt_index();
   f->n_bands = prog->n_bands;
   f->band_type = prog->band_type;
@@ -1390,5 +1405,120 @@ static int index_apply_impl(lt_ctx* c, const lt_index* f, const lt_index_io* io,
     HIP_OR_FAIL(c, hipModuleLaunchKernel(f->fn, gx, (unsigned)io->n_obs, 1, 256, 1, 1, 0,
                                          (hipStream_t)stream_, args, nullptr));
   }
+  return LT_OK;
+}
+
+// ---- mask stage (lt_mask.h) -------------------------------------------------------------------
+int lt_mask_codegen(const lt_index_prog* prog, char* buf, int64_t cap) {
+  if (!prog) return LT_ERR_ARG;
+  std::string err;
+  const std::string src = lt_msk::codegen(*prog, err);
+  if (src.empty()) return LT_ERR_ARG;
+  if (buf && cap > 0) {
+    const size_t n = src.size() < (size_t)(cap - 1) ? src.size() : (size_t)(cap - 1);
+    memcpy(buf, src.data(), n);
+    buf[n] = 0;
+  }
+  return (int)src.size();
+}
+
+int lt_mask_compile(lt_ctx* c, const lt_index_prog* prog, lt_mask** out) {
+  if (!c) return LT_ERR_ARG;
+  if (!prog || !out) return fail(c, LT_ERR_ARG, "null argument%s");
+  *out = nullptr;
+  std::string err;
+  const std::string src = lt_msk::codegen(*prog, err);
+  if (src.empty()) return fail(c, LT_ERR_ARG, "%s", err.c_str());
+  auto it = c->mask_fns.find(src);
+  if (it != c->mask_fns.end()) {
+    *out = it->second;
+    return LT_OK;
+  }
+  std::vector<char> code;
+  const int rc = generated_compile(c, src, "lt_mask.hip", code);
+  if (rc != LT_OK) return rc;
+  lt_mask* f = new lt_mask();
+  f->n_bands = prog->n_bands;
+  f->band_type = prog->band_type;
+  bool ok = hipModuleLoadData(&f->mod, code.data()) == hipSuccess &&
+            hipModuleGetFunction(&f->fn, f->mod, "lt_mask_kernel") == hipSuccess;
+  for (int i = 0; ok && i < 3; i++) {
+    if (lt_msk::kWidths[i] > lt_msk::max_width(f->band_type)) continue;
+    const std::string name = "lt_mask_kernel_v" + std::to_string(lt_msk::kWidths[i]);
+    ok = hipModuleGetFunction(&f->fnv[i], f->mod, name.c_str()) == hipSuccess;
+  }
+  if (!ok) {
+    if (f->mod) (void)hipModuleUnload(f->mod);
+    delete f;
+    return fail(c, LT_ERR_JIT, "module load failed%s");
+  }
+  c->mask_fns[src] = f;
+  *out = f;
+  return LT_OK;
+}
+
+int lt_mask_apply(lt_ctx* c, const lt_mask* f, const lt_mask_io* io, void* stream_) {
+  if (!c) return LT_ERR_ARG;
+  if (!f || !io) return fail(c, LT_ERR_ARG, "null argument%s");
+  if (io->n_pix < 0 || io->n_obs < 0 || io->n_obs > 65535) return fail(c, LT_ERR_ARG, "bad sizes%s");
+  if (io->obs_stride < 0 || io->band_stride < 0 || io->band_pix_stride < 1 ||
+      io->valid_stride < 0 || (io->n_obs > 1 && io->valid_stride < io->n_pix))
+    return fail(c, LT_ERR_ARG, "bad strides%s");
+  if (io->n_pix == 0 || io->n_obs == 0) return LT_OK;
+  if (!io->bands || !io->valid) return fail(c, LT_ERR_ARG, "null buffer%s");
+  HIP_OR_FAIL(c, hipSetDevice(c->device));
+  hipStream_t stream = (hipStream_t)stream_;
+  long long obs_stride = io->obs_stride, band_stride = io->band_stride,
+            pix_stride = io->band_pix_stride, valid_stride = io->valid_stride;
+  unsigned long long* dropped = (unsigned long long*)io->dropped;
+  const long long bsz = (long long)lt_idx::type_size(f->band_type);
+  const unsigned gy = (unsigned)io->n_obs;
+  // blocks per row: what the row needs, capped so that the launch has about kTargetBlocks in all
+  // (the kernels loop over their row)
+  const long long cap = lt_msk::kTargetBlocks / io->n_obs > 0 ? lt_msk::kTargetBlocks / io->n_obs : 1;
+  auto blocks = [&](long long n_threads) -> unsigned {
+    const long long need = (n_threads + 255) / 256;
+    return (unsigned)(need < cap ? need : cap);
+  };
+  // pixels [p0, p0 + n) through the scalar kernel
+  auto scalar = [&](long long p0, long long n) -> hipError_t {
+    const void* bands = (const char*)io->bands + p0 * pix_stride * bsz;
+    unsigned char* valid = io->valid + p0;
+    void* args[] = {(void*)&bands, &obs_stride, &band_stride, &pix_stride, &n, (void*)&valid,
+                    &valid_stride, (void*)&dropped};
+    return hipModuleLaunchKernel(f->fn, blocks(n), gy, 1, 256, 1, 1, 0, stream, args, nullptr);
+  };
+  // The widest vector kernel whose W-element band loads and W-byte validity loads are naturally
+  // aligned from some head offset h < W on: every row and plane stride a multiple of W, and the
+  // band planes (in elements) and the validity rows (in bytes) at the same offset modulo W.
+  long long head = 0, nvec = 0;
+  hipFunction_t fv = nullptr;
+  int width = 0;
+  if (pix_stride == 1 && (uintptr_t)io->bands % (uintptr_t)bsz == 0) {
+    const uintptr_t be = (uintptr_t)io->bands / (uintptr_t)bsz, ve = (uintptr_t)io->valid;
+    for (int i = 0; i < 3 && !fv; i++) {
+      const long long W = lt_msk::kWidths[i];
+      if (!f->fnv[i] || io->n_pix < W) continue;
+      if ((io->n_obs > 1 && (obs_stride % W || valid_stride % W)) ||
+          (f->n_bands > 1 && band_stride % W) || be % W != ve % W)
+        continue;
+      const long long h = (long long)((W - be % W) % W);
+      if (io->n_pix - h < W) continue;
+      fv = f->fnv[i];
+      width = (int)W;
+      head = h;
+      nvec = (io->n_pix - h) / W * W;
+    }
+  }
+  if (head > 0) HIP_OR_FAIL(c, scalar(0, head));
+  if (nvec > 0) {
+    const void* bands = (const char*)io->bands + head * bsz;
+    unsigned char* valid = io->valid + head;
+    void* args[] = {(void*)&bands, &obs_stride, &band_stride, &nvec, (void*)&valid,
+                    &valid_stride, (void*)&dropped};
+    HIP_OR_FAIL(c, hipModuleLaunchKernel(fv, blocks(nvec / width), gy, 1, 256, 1, 1, 0, stream,
+                                         args, nullptr));
+  }
+  if (head + nvec < io->n_pix) HIP_OR_FAIL(c, scalar(head + nvec, io->n_pix - head - nvec));
   return LT_OK;
 }

@@ -47,6 +47,9 @@ inline size_t type_size(int t) {
   }
 }
 inline bool is_unsigned(int t) { return t == LT_T_U16 || t == LT_T_U8 || t == LT_T_U32; }
+inline bool is_int(int t) { return ctype(t) && !is_float(t); }
+// node types of a mask program (lt_mask.h): the raster types and LT_T_BOOL
+inline const char* ctype_m(int t) { return t == LT_T_BOOL ? "bool" : ctype(t); }
 // integer range of a type (for the saturating store)
 inline void int_range(int t, long long& lo, long long& hi) {
   switch (t) {
@@ -102,7 +105,7 @@ struct Val {
 // expression of value v converted to type t (numpy casts every operand to the node's type)
 inline std::string cast_to(const Val& v, int t) {
   if (v.type == t) return v.name;
-  return std::string("((") + ctype(t) + ")" + v.name + ")";
+  return std::string("((") + ctype_m(t) + ")" + v.name + ")";
 }
 
 inline std::string fmt_double(double d) {
@@ -115,8 +118,10 @@ inline std::string fmt_double(double d) {
 // thread, any pixel stride), lt_index_kernel4 (four consecutive pixels per thread, vector loads
 // and stores, for 4-aligned planar bands) and lt_index_kernel4i (the same for pixel-interleaved
 // bands); the host sends the tail to the scalar one.
+// mask: a mask program (lt_mask.h) — the comparison / bitwise / shift nodes are admitted, the
+// root must be a LT_T_BOOL and store_out is its name; out_type is not read.
 inline std::string codegen_body(const lt_index_prog& P, bool vec, std::string& err,
-                                std::string& store_out);
+                                std::string& store_out, bool mask = false);
 inline std::string codegen(const lt_index_prog& P, std::string& err) {
   std::string store1, store4;
   const std::string body1 = codegen_body(P, false, err, store1);
@@ -177,9 +182,9 @@ inline std::string codegen(const lt_index_prog& P, std::string& err) {
 }
 
 inline std::string codegen_body(const lt_index_prog& P, bool vec, std::string& err,
-                                std::string& store_out) {
+                                std::string& store_out, bool mask) {
   if (P.n_ops < 1 || P.n_ops > LT_MAX_PROG || P.n_bands < 1 || P.n_bands > LT_MAX_BANDS ||
-      !ctype(P.band_type) || !ctype(P.out_type)) {
+      !ctype(P.band_type) || (!mask && !ctype(P.out_type))) {
     err = "index program: bad sizes or types";
     return "";
   }
@@ -189,11 +194,12 @@ inline std::string codegen_body(const lt_index_prog& P, bool vec, std::string& e
   for (int k = 0; k < P.n_ops; k++) {
     const lt_index_op& o = P.ops[k];
     const std::string v = "v" + std::to_string(k);
-    if (!ctype(o.type)) {
+    const char* T = mask ? ctype_m(o.type) : ctype(o.type);
+    if (!T) {
       err = "index program: bad node type";
       return "";
     }
-    const char* T = ctype(o.type);
+    const bool is_b = o.type == LT_T_BOOL;  // (mask programs only: ctype() has no boolean)
     switch (o.op) {
       case LT_OP_BAND:
         if (o.ival < 0 || o.ival >= P.n_bands || o.type != P.band_type) {
@@ -210,6 +216,11 @@ inline std::string codegen_body(const lt_index_prog& P, bool vec, std::string& e
         st.push_back({v, o.type});
         break;
       case LT_OP_CONST_I:
+        if (is_b) {  // a folded boolean
+          body += "  const bool " + v + (o.ival != 0 ? " = true;\n" : " = false;\n");
+          st.push_back({v, LT_T_BOOL});
+          break;
+        }
         snprintf(line, sizeof line, "  const long long %s = %lldLL;\n", v.c_str(),
                  (long long)o.ival);
         body += line;
@@ -230,6 +241,10 @@ inline std::string codegen_body(const lt_index_prog& P, bool vec, std::string& e
         }
         Val a = st.back();
         st.pop_back();
+        if (is_b || a.type == LT_T_BOOL) {
+          err = "mask program: arithmetic on a boolean";
+          return "";
+        }
         std::string e;
         if (is_float(o.type))
           e = "-" + cast_to(a, o.type);
@@ -252,6 +267,10 @@ inline std::string codegen_body(const lt_index_prog& P, bool vec, std::string& e
         st.pop_back();
         Val a = st.back();
         st.pop_back();
+        if (is_b || a.type == LT_T_BOOL || b.type == LT_T_BOOL) {
+          err = "mask program: arithmetic on a boolean";
+          return "";
+        }
         const std::string x = cast_to(a, o.type), y = cast_to(b, o.type);
         std::string e;
         if (is_float(o.type)) {
@@ -274,6 +293,83 @@ inline std::string codegen_body(const lt_index_prog& P, bool vec, std::string& e
         st.push_back({v, o.type});
         break;
       }
+      case LT_OP_EQ: case LT_OP_NE: case LT_OP_LT: case LT_OP_LE: case LT_OP_GT: case LT_OP_GE:
+      case LT_OP_AND: case LT_OP_OR: case LT_OP_XOR: {
+        if (!mask) {
+          err = "index program: bad opcode";
+          return "";
+        }
+        if (st.size() < 2) {
+          err = "mask program: stack underflow";
+          return "";
+        }
+        Val b = st.back();
+        st.pop_back();
+        Val a = st.back();
+        st.pop_back();
+        const bool cmp = o.op <= LT_OP_GE;
+        // booleans meet only booleans (== != & | ^); a bitwise node is an integer node
+        if ((a.type == LT_T_BOOL) != is_b || (b.type == LT_T_BOOL) != is_b ||
+            (is_b && cmp && o.op != LT_OP_EQ && o.op != LT_OP_NE) ||
+            (!cmp && !is_b && (!is_int(o.type) || !is_int(a.type) || !is_int(b.type)))) {
+          err = "mask program: bad operand types";
+          return "";
+        }
+        static const char* const sym[] = {" == ", " != ", " < ", " <= ", " > ", " >= ",
+                                          " & ", " | ", " ^ "};
+        const std::string e = cast_to(a, o.type) + sym[o.op - LT_OP_EQ] + cast_to(b, o.type);
+        if (cmp || is_b) {
+          body += "  const bool " + v + " = (bool)(" + e + ");\n";
+          st.push_back({v, LT_T_BOOL});
+        } else {
+          body += std::string("  const ") + T + " " + v + " = (" + T + ")(" + e + ");\n";
+          st.push_back({v, o.type});
+        }
+        break;
+      }
+      case LT_OP_NOT:
+      case LT_OP_SHL:
+      case LT_OP_SHR: {
+        if (!mask) {
+          err = "index program: bad opcode";
+          return "";
+        }
+        if (st.empty()) {
+          err = "mask program: stack underflow";
+          return "";
+        }
+        Val a = st.back();
+        st.pop_back();
+        if (is_b) {
+          if (o.op != LT_OP_NOT || a.type != LT_T_BOOL) {
+            err = "mask program: bad operand types";
+            return "";
+          }
+          body += "  const bool " + v + " = !" + a.name + ";\n";
+          st.push_back({v, LT_T_BOOL});
+          break;
+        }
+        if (!is_int(o.type) || !is_int(a.type)) {
+          err = "mask program: bitwise operator on a non-integer";
+          return "";
+        }
+        const std::string x = cast_to(a, o.type);
+        std::string e;
+        if (o.op == LT_OP_NOT) {
+          e = "~" + x;
+        } else {
+          if (o.ival < 0 || o.ival >= (long long)(8 * type_size(o.type))) {
+            err = "mask program: shift count out of range";
+            return "";
+          }
+          const std::string n = std::to_string((long long)o.ival);
+          e = o.op == LT_OP_SHL ? "(unsigned long long)(long long)" + x + " << " + n  // wraps
+                                : x + " >> " + n;
+        }
+        body += std::string("  const ") + T + " " + v + " = (" + T + ")(" + e + ");\n";
+        st.push_back({v, o.type});
+        break;
+      }
       default:
         err = "index program: bad opcode";
         return "";
@@ -282,6 +378,14 @@ inline std::string codegen_body(const lt_index_prog& P, bool vec, std::string& e
   if (st.size() != 1) {
     err = "index program: stack not balanced";
     return "";
+  }
+  if (mask) {
+    if (st.back().type != LT_T_BOOL) {
+      err = "mask program: the root is not a boolean";
+      return "";
+    }
+    store_out = st.back().name;
+    return body;
   }
   // the store into the template's type (GDAL's conversion; parity-unpinned, index_eqn.py)
   const Val r = st.back();
@@ -312,8 +416,6 @@ inline std::string codegen_body(const lt_index_prog& P, bool vec, std::string& e
   store_out = store;
   return body;
 }
-
-inline bool is_int(int t) { return ctype(t) && !is_float(t); }
 
 // A program's integer linear form (lt_abi.h lt_index_lin), or false. Every arithmetic node must
 // carry the one integer type W (numpy wraps each node modulo 2^bits(W), so the whole sum taken

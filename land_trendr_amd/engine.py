@@ -279,6 +279,55 @@ class Engine:
                                             ctypes.c_void_p(st.cuda_stream)), 'lt_index_apply')
         return out
 
+    # --- mask stage: mask_eqn (rast_algebra's mask_eqn, utils.py:447-484; lt_mask.h) ---
+    def compile_mask(self, program):
+        """hiprtc-compile an index_eqn.MaskProgram for this device (cached per program)."""
+        fn = ctypes.c_void_p()
+        prog = program.to_c()
+        with torch.cuda.device(self.device):
+            self._check(self.lib.lt_mask_compile(self.ctx, ctypes.byref(prog), ctypes.byref(fn)),
+                        'lt_mask_compile')
+        return MaskFn(fn, program)
+
+    def apply_mask(self, fn, bands, valid, dropped=None, stream=None):
+        """valid[k, p] &= mask_eqn on the bands of obs k at pixel p, in place. bands: [K, NB, P]
+        planes in the program's band type (NB = len(program.band_numbers); any strides: a view of
+        a larger stack, pixel-interleaved, ...); valid: uint8 [K, P] with unit pixel stride (its
+        row stride may exceed P). dropped: an int64 [1] device tensor the number of bytes cleared
+        is added to. Asynchronous on `stream`; returns valid."""
+        prog = fn.program
+        want = _TORCH_OF_LT[_LT_T_OF_NP(prog.band_dtype)]
+        NB = len(prog.band_numbers)
+        if (bands.dim() != 3 or bands.dtype != want or bands.device != self.device or
+                bands.shape[1] != NB):
+            raise LtError('bands must be a %s [K, %d, P] tensor on %s' % (want, NB, self.device))
+        K, _, P = bands.shape
+        if (valid.dim() != 2 or valid.dtype != torch.uint8 or valid.device != self.device or
+                tuple(valid.shape) != (K, P) or (P > 1 and valid.stride(1) != 1) or
+                (K > 1 and valid.stride(0) < P)):
+            raise LtError('valid must be a uint8 [%d, %d] tensor on %s with unit pixel stride'
+                          % (K, P, self.device))
+        if K > 65535:
+            raise LtError('at most 65535 observations')
+        if dropped is not None and (dropped.dtype != torch.int64 or dropped.numel() != 1 or
+                                    dropped.device != self.device):
+            raise LtError('dropped must be an int64 tensor of one element on %s' % self.device)
+        if K == 0 or P == 0:
+            return valid
+        io = _abi.LtMaskIO()
+        io.n_pix, io.n_obs = P, K
+        io.obs_stride, io.band_stride = bands.stride(0), bands.stride(1)
+        io.band_pix_stride = bands.stride(2) if P > 1 else 1
+        io.bands, io.valid = bands.data_ptr(), valid.data_ptr()
+        io.valid_stride = valid.stride(0) if K > 1 else P
+        io.dropped = dropped.data_ptr() if dropped is not None else None
+        if min(io.obs_stride, io.band_stride) < 0 or io.band_pix_stride < 1:
+            raise LtError('bands must have positive pixel stride and non-negative strides')
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        self._check(self.lib.lt_mask_apply(self.ctx, fn.handle, ctypes.byref(io),
+                                           ctypes.c_void_p(st.cuda_stream)), 'lt_mask_apply')
+        return valid
+
     # --- output raster assembly (output_reducer -> data2raster, lt_raster_assemble) ---
     def raster_assemble(self, jobs, stream=None):
         """jobs: a list of _abi.LtRasterJob (device pointers of this engine's tensors, which the
@@ -592,6 +641,14 @@ class IndexFn:
         if self._handle is None and self._build is not None:
             self._handle, self._build = self._build(), None
         return self._handle
+
+
+class MaskFn:
+    """A compiled mask_eqn kernel (owned by the engine's context)."""
+
+    def __init__(self, handle, program):
+        self.handle = handle
+        self.program = program
 
 
 def linear_form(program):

@@ -11,7 +11,10 @@ without mrjob, EMR or S3, over a job directory laid out like the reference's S3 
 Steps, as the reference chains them:
   1. setup    (setup_mapper :20-45)   analysis rasters by RAST_TRIGGER, grid from the first one;
   2. parse    (parse_mapper :47-81)   ingest.ingest_stack: band samples + mask validity per grid
-                                      point (index_eqn runs on the GPU in step 3);
+                                      point (index_eqn runs on the GPU in step 3, and so does
+                                      the optional settings.json mask_eqn, a boolean expression
+                                      over the same bands that drops observations as a mask
+                                      raster does: its bands are ingested with index_eqn's);
   3. analysis (analysis_reducer :83-126) the mosaic path of runner.py over pixel tiles on the GPU
                                       (tiles round-robin over the torchrun ranks; the label planes
                                       go to rank 0 over RCCL, the per-year trendline planes stream
@@ -134,6 +137,11 @@ class LocalJob:
         self.sample = sample
         # rasters sampled on the device (Engine.sample_grid), cloud masks by where they were applied
         self.sample_stats = {'rasters': 0, 'masks_device': 0, 'masks_host': 0}
+        # settings.json mask_eqn: {'eqn', 'observations' (valid observation-pixels of this rank's
+        # tiles before the mask), 'dropped' (those the mask cleared)} once analyze() has run; None
+        # without the key. stack['valid'] keeps the ingest validity (coverage and cloud masks): the
+        # mask is ANDed into the planes the analysis reads, not into the stack
+        self.mask_stats = None
         self.decode_times = {}  # device mode: thread-seconds of parse() inside the decoder
         self._stack_meta = None  # device mode: (sample type, [K, nb, Q]) of the device stack
         self._dev_keep = None    # device mode: the device stack behind stack['bands']
@@ -294,7 +302,10 @@ class LocalJob:
         _, world, rank = self._dist()
         P = len(self.grid_xy[0])
         self.mosaic = Mosaic([P], self.tile_pixels, world, rank, 'round_robin')
-        eqn_bands = sorted(parse_eqn_bands(self.settings['index_eqn']))
+        # the planes ingested: the bands of index_eqn and, if set, of mask_eqn (the reference's
+        # all_bands, utils.py:459-461)
+        eqn_bands = sorted(set(parse_eqn_bands(self.settings['index_eqn'])) |
+                           set(parse_eqn_bands(self.settings.get('mask_eqn') or '')))
         # on a GPU (LT_JOB_UPLOAD=whole), each raster's planes cross to the device as soon as they
         # are decoded, on the worker that decoded them, while the other rasters decode: analyze()
         # then starts from the device stack
@@ -537,7 +548,7 @@ class LocalJob:
         import torch
         from .distributed import TrendlineStream
         from .engine import _DTYPE, LABELS, TRENDLINE, get_engine, pack_valid_bits
-        from .index_eqn import IndexProgram
+        from .index_eqn import IndexProgram, MaskProgram
         from .runner import MosaicRunner, TileInput
         from .scene import build_scene, parse_date
         from .settings import compile_params
@@ -565,6 +576,30 @@ class LocalJob:
                             raster_count=max(numbers))
         slots = [numbers.index(b) for b in prog.bands]  # the planes the equation reads
         fn = eng.compile_index(prog)
+        # mask_eqn: a boolean expression over the same planes, ANDed into the validity the
+        # analysis reads (stack['valid'] keeps the ingest validity). On the GPU one streaming
+        # pass (Engine.apply_mask) over the device stack, or over each tile's planes in the
+        # 'tile' upload mode; an engine without apply_mask (the tests' CPU double) gets
+        # MaskProgram.evaluate's numpy result.
+        self.mask_stats = None
+        mprog = mfn = None
+        m_obs = m_drop = 0  # valid observation-pixels before the mask, and those it dropped
+        m_events = []
+        if self.settings.get('mask_eqn'):
+            mprog = MaskProgram(self.settings['mask_eqn'], b_dtype, numbers,
+                                raster_count=max(numbers))
+            if hasattr(eng, 'apply_mask'):
+                mfn = eng.compile_mask(mprog)
+                m_drop = torch.zeros(1, dtype=torch.int64, device=dev)
+
+        def mask_device(bands, valid):  # valid &= mask on device planes, in place
+            nonlocal m_obs
+            m_obs = m_obs + valid.count_nonzero()
+            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            ev[0].record(torch.cuda.current_stream(dev))
+            eng.apply_mask(mfn, bands, valid, dropped=m_drop)
+            ev[1].record(torch.cuda.current_stream(dev))
+            m_events.append(ev)
         m = self.mosaic
         if (m.world, m.rank, m.scene_pixels) != (world, rank, [P]):
             raise RuntimeError('parse() ran under another process group')
@@ -590,7 +625,14 @@ class LocalJob:
                 w_bands = torch.from_numpy(st['bands']).to(dev)
                 w_valid = torch.from_numpy(st['valid']).to(dev)
             self._dev_stack = None
-            if slots != list(range(b_shape[1])):
+            if mfn is not None:
+                if w_valid is getattr(self, '_dev_keep_valid', None):
+                    w_valid = w_valid.clone()  # (stack['valid'] comes down from that tensor)
+                mask_device(w_bands, w_valid)
+            if slots == list(range(slots[0], slots[0] + len(slots))):
+                # (a run of planes of a stack that also holds mask_eqn's: a view, no copy)
+                w_bands = w_bands[:, slots[0]:slots[0] + len(slots)]
+            elif slots != list(range(b_shape[1])):
                 w_bands = w_bands[:, slots]
         items = []
         for t in m.mine:
@@ -600,8 +642,19 @@ class LocalJob:
                 valid = w_valid[:, q:q + t.n]
             else:
                 t_bands, t_valid = stack_range(st, t.p0, t.p1)
-                bands = torch.from_numpy(np.ascontiguousarray(t_bands[:, slots])).to(dev)
+                if mprog is not None and mfn is None:  # no HIP engine: the numpy evaluation
+                    keep = mprog.evaluate(np.moveaxis(t_bands, 1, 0))
+                    m_obs += int(np.count_nonzero(t_valid))
+                    m_drop += int(np.count_nonzero((t_valid != 0) & ~keep))
+                    t_valid = np.where(keep, t_valid, 0).astype(np.uint8)
                 valid = torch.from_numpy(np.ascontiguousarray(t_valid)).to(dev)
+                if mfn is not None:  # the mask reads every plane of the tile
+                    bands = torch.from_numpy(np.ascontiguousarray(t_bands)).to(dev)
+                    mask_device(bands, valid)
+                    if slots != list(range(b_shape[1])):
+                        bands = bands[:, slots].contiguous()
+                else:
+                    bands = torch.from_numpy(np.ascontiguousarray(t_bands[:, slots])).to(dev)
             if cuda and fn.lin is not None and len(slots) == 2 and bands.dtype == torch.int16:
                 # the fused load stage reads a pixel's two int16 bands as one 32-bit word
                 inter = torch.empty((K, t.n, 2), dtype=bands.dtype, device=dev).permute(0, 2, 1)
@@ -621,6 +674,11 @@ class LocalJob:
         if cuda:
             torch.cuda.synchronize(dev)
         self.analyze_s = {'inputs': time.perf_counter() - t_in}
+        if mprog is not None:
+            self.mask_stats = {'eqn': mprog.eqn, 'observations': int(m_obs),
+                               'dropped': int(m_drop)}
+            if m_events:  # the mask kernels' time on the device
+                self.analyze_s['mask'] = sum(a.elapsed_time(b) for a, b in m_events) * 1e-3
         host = self.host_trendline = self._trendline_planes(tl_fields, Y, P, dist, world, rank)
         # the trendline planes: a ring of three tiles' buffers on the GPU (tile k reuses tile
         # k-3's once its rows have reached the host), so a rank's HBM never holds all its tiles'

@@ -140,17 +140,37 @@ def analysis_reducer_batch(dates, values, valid, settings, fields=LABELS + ('sta
     bands: instead of values, the raw band planes [K, n_bands, P] (their dtype is the raster's);
     settings['index_eqn'] is then evaluated on the GPU first (parse_mapper's rast_algebra,
     mr_land_trendr_job.py:67-68). band_numbers: the reference band number of each plane (default
-    1..n_bands)."""
+    1..n_bands). settings['mask_eqn'], if present, is evaluated on the same planes and ANDed into
+    a copy of valid (all ones when valid is None): the caller's tensor is not modified."""
     settings = load_settings(settings)
     scene = build_scene(dates, parse_date(settings['target_date']))
     params, rules = compile_params(settings['line_cost'], settings.get('label_rules', ()),
                                    pre_threshold_mode)
     if bands is not None:
+        if settings.get('mask_eqn'):
+            valid = mask_tile(settings['mask_eqn'], bands, valid, band_numbers, device=device)
         values = index_tile(settings['index_eqn'], bands, band_numbers, device=device)
     out = analyze_tile(scene, params, values, valid, fields, device=device)
     out['_scene'] = scene
     out['_rules'] = rules
     return out
+
+
+def mask_tile(mask_eqn, bands, valid=None, band_numbers=None, device=None):
+    """rast_algebra's mask_eqn on the GPU: bands [K, n_bands, P] -> a new validity plane [K, P]
+    uint8, `valid` (ones when None) cleared where the expression is false."""
+    import torch
+    from .index_eqn import MaskProgram
+    eng = get_engine(device)
+    K, nb, P = bands.shape
+    numbers = list(band_numbers) if band_numbers is not None else list(range(1, nb + 1))
+    prog = MaskProgram(mask_eqn, np.dtype(str(bands.dtype).replace('torch.', '')), numbers,
+                       raster_count=max(numbers))
+    if valid is None:
+        out = torch.ones((K, P), dtype=torch.uint8, device=bands.device)
+    else:
+        out = valid.clone(memory_format=torch.contiguous_format)
+    return eng.apply_mask(eng.compile_mask(prog), bands, out)
 
 
 def index_tile(index_eqn, bands, band_numbers=None, device=None):

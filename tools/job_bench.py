@@ -16,6 +16,13 @@ would, on cuda:0, and the script prints one JSON line:
     python tools/job_bench.py --rows 7000 --cols 7000 --years 30 [--trendline] [--check 20000]
                               [--decode {host,device}] [--encode {host,device}]
                               [--sample {host,device}] [--shift N] [--mask PROB]
+                              [--mask-eqn EQN | --qa-cloudmask]
+
+--mask-eqn EQN: the rasters carry a third band, a QA band that is 0 with the --mask probability
+and 1 elsewhere, instead of cloudmask rasters; settings.json gets mask_eqn EQN (e.g. 'B3 != 0') and
+the line reports LocalJob.mask_stats and the mask pass's device time. --qa-cloudmask: the same
+three-band rasters, but the QA band reaches the job as `_cloudmask` rasters and no mask_eqn is
+set: the job the mask_eqn one is compared with.
 """
 import argparse
 import json
@@ -35,13 +42,16 @@ SETTINGS = {'index_eqn': 'B1 - B2', 'line_cost': 10, 'target_date': '2014-07-01'
             'label_rules': [{'name': 'gd', 'val': 1, 'change_type': 'GD'}]}
 
 
-def make_stack(root, job, rows, cols, years, seed, mask_prob, shift=0):
+def make_stack(root, job, rows, cols, years, seed, mask_prob, shift=0, mask_eqn=None,
+               qa_band=False):
     """The job directory: one two-band int16 LZW GeoTIFF per acquisition date (raster order:
     pixel p of the scene at row p // cols, column p % cols) and, with mask_prob > 0, a cloudmask
     raster per date. shift = N > 0: every N-th raster is written with an extent of its own — its
     origin a few pixels off the template's in both axes, a few rows and columns larger or smaller
     (alternating), zeros outside the scene — and with two spare bands behind the two the index
-    reads, as a LEDAPS stack's dates differ. Returns (seconds, bytes written)."""
+    reads, as a LEDAPS stack's dates differ. mask_eqn / qa_band: every raster gets a third band
+    (0 where the scene's mask is, 1 elsewhere); with mask_eqn the key goes into settings.json and
+    no cloudmask raster is written. Returns (seconds, bytes written)."""
     import torch
     from land_trendr_amd.raster import write_geotiff
     from land_trendr_amd.synth import make_scene
@@ -49,7 +59,7 @@ def make_stack(root, job, rows, cols, years, seed, mask_prob, shift=0):
     rdir = os.path.join(root, job, 'input', 'rasters')
     os.makedirs(rdir, exist_ok=True)
     with open(os.path.join(root, job, 'input', 'settings.json'), 'w') as f:
-        json.dump(SETTINGS, f)
+        json.dump(dict(SETTINGS, mask_eqn=mask_eqn) if mask_eqn else SETTINGS, f)
     dev = 'cuda' if torch.cuda.is_available() else 'cpu'
     sc = make_scene(rows * cols, n_years=years, k_min=1, k_max=1, mask_prob=mask_prob, seed=seed,
                     device=dev, with_bands=True)
@@ -58,21 +68,26 @@ def make_stack(root, job, rows, cols, years, seed, mask_prob, shift=0):
     for k, d in enumerate(sc.dates):
         stem = 'LT5045029_%d_%03d_20120124_104859' % (d.year, d.timetuple().tm_yday)
         img = sc.bands[k].reshape(2, rows, cols).cpu().numpy()
+        if mask_eqn or qa_band:
+            qa = (np.ones((1, rows, cols), img.dtype) if sc.valid is None else
+                  sc.valid[k].reshape(1, rows, cols).cpu().numpy().astype(img.dtype))
+            img = np.concatenate([img, qa])
         fn = os.path.join(rdir, stem + '_ledaps.tif')
         gt = GT
         if shift > 0 and k % shift == shift - 1:
             # raster pixel (y, x) is template pixel (y + sy, x + sx)
             sgn = 1 if (k // shift) % 2 == 0 else -1
             sx, sy, h, w = 3 * sgn, -2 * sgn, rows + 5 * sgn, cols - 4 * sgn
-            big = np.zeros((4, h, w), img.dtype)
+            nb = img.shape[0]
+            big = np.zeros((nb + 2, h, w), img.dtype)
             y0, y1, x0, x1 = max(0, -sy), min(h, rows - sy), max(0, -sx), min(w, cols - sx)
-            big[:2, y0:y1, x0:x1] = img[:, y0 + sy:y1 + sy, x0 + sx:x1 + sx]
-            big[2:] = 7
+            big[:nb, y0:y1, x0:x1] = img[:, y0 + sy:y1 + sy, x0 + sx:x1 + sx]
+            big[nb:] = 7
             img = big
             gt = (GT[0] + sx * GT[1], GT[1], 0.0, GT[3] + sy * GT[5], 0.0, GT[5])
         write_geotiff(fn, img, geotransform=gt, nodata=None)
         nbytes += os.path.getsize(fn)
-        if sc.valid is not None:
+        if sc.valid is not None and not mask_eqn:
             m = sc.valid[k].reshape(rows, cols).cpu().numpy()
             mf = os.path.join(rdir, stem + '_cloudmask.tif')
             write_geotiff(mf, m, geotransform=GT, nodata=None)
@@ -102,8 +117,13 @@ def check_sample(j, n, seed=11):
     idx = (b[:, 0].astype(np.int32) - b[:, 1]).astype(np.int16)
     meta = build_scene(st['dates'], parse_date(SETTINGS['target_date']))
     params, _ = compile_params(SETTINGS['line_cost'], SETTINGS['label_rules'])
-    exp = oracle.analyze_tile(meta, params, idx.astype(np.float64),
-                              np.ascontiguousarray(st['valid'][:, cols_s]),
+    valid = np.ascontiguousarray(st['valid'][:, cols_s])
+    if j.settings.get('mask_eqn'):  # the numpy evaluation of the mask on the same samples
+        from land_trendr_amd.index_eqn import MaskProgram
+        keep = MaskProgram(j.settings['mask_eqn'], b.dtype, st['band_numbers']).evaluate(
+            np.moveaxis(b, 1, 0))
+        valid = np.where(keep, valid, 0).astype(np.uint8)
+    exp = oracle.analyze_tile(meta, params, idx.astype(np.float64), valid,
                               n_threads=host_threads())
     bad = np.flatnonzero(exp['status'] & ~_abi.LT_ST_EMPTY)  # on_error='skip'
     exp['matched'][:, bad] = 0
@@ -180,6 +200,12 @@ def main():
     ap.add_argument('--shift', type=int, default=0,
                     help='N > 0: every N-th raster gets an extent of its own (a few pixels off in '
                          'both axes, a few rows and columns larger or smaller) and two spare bands')
+    ap.add_argument('--mask-eqn', default=None,
+                    help="settings.json mask_eqn over a QA band B3 (0 with the --mask probability) "
+                         "that replaces the cloudmask rasters, e.g. 'B3 != 0'")
+    ap.add_argument('--qa-cloudmask', action='store_true',
+                    help='the three-band rasters of --mask-eqn, masked through cloudmask rasters '
+                         'instead (no mask_eqn): the job to compare with')
     ap.add_argument('--encode', default='host', choices=('host', 'device'),
                     help="where the output rasters' strips are encoded (LocalJob encode=): "
                          'liblt_io.so on the host threads, or the HIP strip encoder on the GPU')
@@ -191,7 +217,7 @@ def main():
     os.makedirs(a.work)
     try:
         gen_s, in_bytes = make_stack(a.work, 'bench', a.rows, a.cols, a.years, a.seed, a.mask,
-                                        a.shift)
+                                        a.shift, a.mask_eqn, a.qa_cloudmask)
         print('stack written: %.1f s, %.2f GB' % (gen_s, in_bytes / 1e9), file=sys.stderr,
               flush=True)
         P = a.rows * a.cols
@@ -222,7 +248,8 @@ def main():
             print('%s %.2f s' % (step, t[step]), file=sys.stderr, flush=True)
         total = sum(t.values())
         K = len(j.stack['dates'])
-        decoded = K * 2 * P * 2  # two int16 bands per acquisition
+        nb = len(j.stack['band_numbers'])
+        decoded = K * nb * P * 2  # the int16 bands ingested per acquisition (two without a mask_eqn)
         out_bytes = sum(os.path.getsize(p) for v in files.values() for p in v)
         res = {'workload': 'job: %d x %d px x %d acquisitions, 2 int16 bands each (LZW GeoTIFF), '
                            "index_eqn 'B1 - B2', line_cost 10, one GD rule%s"
@@ -246,6 +273,18 @@ def main():
                'encode': a.encode, 'encode_stats': j.encode_stats,
                'decode_times_s': {k: round(v, 3)
                                   for k, v in getattr(j, 'decode_times', {}).items()}}
+        if a.mask_eqn or a.qa_cloudmask:
+            res['mask_eqn'], res['qa_cloudmask'] = a.mask_eqn, a.qa_cloudmask
+            res['mask_stats'] = j.mask_stats
+            ms = getattr(j, 'analyze_s', {}).get('mask')
+            if ms is not None:
+                # the pass reads the planes the expression names and the validity bytes, and
+                # writes back the validity vectors in which it cleared a byte (counted in full)
+                from land_trendr_amd.index_eqn import MaskProgram
+                n_slots = len(MaskProgram(a.mask_eqn, np.int16, j.stack['band_numbers']).slots)
+                nbytes = K * P * (2 * n_slots + 2)
+                res['mask_pass'] = {'ms': round(ms * 1e3, 4), 'bytes': nbytes,
+                                    'tb_per_s': round(nbytes / ms / 1e12, 4)}
         if a.diag:
             res['diag'] = diag(j)
         if a.check > 0:
