@@ -103,6 +103,13 @@ __device__ inline void year_row_store(double v, double* a) {
 #define LT_LINE_COST P.line_cost
 #endif
 
+// the lazy DP's neighbouring-triple exit (lt_pixel.h LT_DP_NEIGHBOUR) in the specialised kernels
+#if LT_DP_NEIGHBOUR && defined(LT_SPEC_NRULES)
+#define LT_DP_NB_SPEC 1
+#else
+#define LT_DP_NB_SPEC 0
+#endif
+
 namespace lt {
 
 // m * Sxx - Sx^2 of a segment's x sums (m <= 64 points, x <= 255: both products below 2^32, the
@@ -965,6 +972,16 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
     double oA = 0.0, oB = 0.0, oC = 0.0, oD = 0.0;  // oA = OPTa[0] for column 0
     // tags of the OPTa window slots (lt_pixel.h tag_order; < 256: the value is exact)
     int gA = 0, gB = 0, gC = 0, gD = 0;
+    // the exit test's neighbouring triples (lt_pixel.h dp_start_bound_nb): E1[j-1] and E1[j-2],
+    // the closed-form residual the last two columns priced as their first start; column j writes
+    // E1[j] over E1[j-2], so the two slots alternate with the unrolled columns (no copies).
+    // The analyze stage's one-rule kernels specialised for a configuration only (LT_DP_NB_SPEC):
+    // they hold the DP in 128 VGPRs without a spill. The resolve stage keeps the exit it had, and
+    // so do the kernels that spill already (several rules, or rules and line cost read from the
+    // launch): every form of the history tried there (binary64 or binary32 registers, LDS
+    // planes) spilled more VGPRs than before (DESIGN.md § (d))
+    constexpr bool NB = LT_DP_NB_SPEC != 0 && !EXACT && RMAX == 1;
+    double hA = 0.0, hB = 0.0;
     double SyyAll = 0.0;                // sum of y^2 over the points 0..j
     const bool prune = c >= 0.0;
     // zero-residual starts of >= 3 points (lt_pixel.h kZero): integer series of int16 range only
@@ -1054,7 +1071,7 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
     auto column = [&](const int j, int& wx0, int& wx1, int& wx2, int& wx3, double& wy0,
                       double& wy1, double& wy2, double& wy3, double& opt_j, double& opt_jm1,
                       double& opt_jm2, double& opt_jm3, int& tg_j, int& tg_jm1, int& tg_jm2,
-                      int& tg_jm3) __attribute__((always_inline)) {
+                      int& tg_jm3, double& h1, double& h2) __attribute__((always_inline)) {
       const bool col = j < n;
       const uint64_t colmask = __ballot(col);
       double Sy = 0.0, Sxy = 0.0, Syy = 0.0;
@@ -1156,8 +1173,10 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
       // whether the segment is exactly collinear with a residual that rounds away (zr)
       // returns whether the interval reaches a zero residual (zero_test decides, where it can
       // matter)
-      auto price = [&](int i, double o, int tg, double& v, double& hi, double& lo,
-                       double& bnd) __attribute__((always_inline)) {
+      // (NB: eh, ok, wk = the neighbouring triples' residual, OPTa[i-1] and its error bound)
+      auto price = [&](int i, double o, int tg, double eh, double ok, double wk, double& v,
+                       double& hi, double& lo, double& bnd, double& eo)
+                       __attribute__((always_inline)) {
         // closed-form SSE: (m*Syy - Sy^2 - N1^2/D) / m, one reciprocal
         const int m = j - i + 1;  // wave-uniform, >= 3
         const double md = (double)m;
@@ -1176,7 +1195,9 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
         const double w = __builtin_fma(0x1p-50, __builtin_fabs(v), ws + wopt);
         hi = v + w;
         lo = v - w;
-        bnd = dp_start_bound_slack(e, o, wopt, c, slack);
+        if constexpr (NB) bnd = dp_start_bound_nb_slack(e, o, wopt, eh, ok, wk, c, slack);
+        else bnd = dp_start_bound_slack(e, o, wopt, c, slack);
+        eo = e;
         return e <= ws;  // (zlane applied by the caller: see zmask)
       };
       // exactly collinear with a residual that rounds away (lt_pixel.h kZero, sse_exact_zero), on
@@ -1210,9 +1231,10 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
       // start i (>= 3 points, its point already in the sums): priced, offered to the trackers when
       // its lower end reaches the column's current upper bound (else it can change no decision),
       // its early-exit bound returned
-      auto one_start = [&](int i, double o, int tg) __attribute__((always_inline)) {
+      auto one_start = [&](int i, double o, int tg, double eh, double ok, double wk, double& eo)
+                           __attribute__((always_inline)) {
         double v, hi, lo, bnd;
-        const bool nz = price(i, o, tg, v, hi, lo, bnd);
+        const bool nz = price(i, o, tg, eh, ok, wk, v, hi, lo, bnd, eo);
         // resolve stage: every start whose interval reaches the column's current upper bound (a
         // NaN bound included) is a candidate of an exact decision
         if constexpr (EXACT) {
@@ -1240,12 +1262,26 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
         return prune && (__ballot(!(bnd > upper())) & colmask) == 0;
       };
       bool more = j >= 2;  // wave-uniform
+      double onext = 0.0, hmax = 0.0;
       if (more) {  // starts j-2 and j-3 from the register window
         add_xy(wx2, wy2);
-        more = !leave(one_start(j - 2, opt_jm2, tg_jm2));
+        // the start below, j-3, contains the triple (j-3, j-2, j-1): E1[j-1]. (j == 2: no start
+        // below; the slot of OPTa[j-3] holds 0 then, a bound no larger than the plain one)
+        double e1;
+        more = !leave(one_start(j - 2, opt_jm2, tg_jm2, h1, opt_jm3, Emax, e1));
+        if constexpr (NB) {  // E1[j] over E1[j-2]
+          hmax = __builtin_fmax(h1, h2);
+          h2 = e1;
+        }
         if (j >= 3 && more) {
+          // OPTa[j-4], the first value the loop below reads, one start ahead: start j-4 and every
+          // lower one contain both neighbouring triples
+          if constexpr (NB) {
+            if (j >= 4) onext = OPTa[j - 4];
+          }
           add_xy(wx3, wy3);
-          more = !leave(one_start(j - 3, opt_jm3, tg_jm3));
+          double eo;
+          more = !leave(one_start(j - 3, opt_jm3, tg_jm3, hmax, onext, Emax, eo));
         }
         more = more && j >= 3;
       }
@@ -1255,8 +1291,15 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
         for (int i = __builtin_amdgcn_readfirstlane(j - 4); i >= 0;
              i = __builtin_amdgcn_readfirstlane(i - 1)) {
           add_xy(L.xn[i][lane], (double)L.ys[i][lane]);
+          double eo;
+          if constexpr (NB) {
+            // OPTa[i-1] one iteration ahead (i == 0: the last start, its test decides nothing)
+            const double o = onext;
+            onext = OPTa[i >= 1 ? i - 1 : 0];
+            if (leave(one_start(i, o, ((exact >> i) & 1) ? 0 : -1, hmax, onext, Emax, eo))) break;
+          } else
           // tags are kept in the window only: a start from private memory is exact or not
-          if (leave(one_start(i, OPTa[i], ((exact >> i) & 1) ? 0 : -1))) break;
+          if (leave(one_start(i, OPTa[i], ((exact >> i) & 1) ? 0 : -1, 0.0, 0.0, 0.0, eo))) break;
         }
       }
       // the group's best enters the trackers (an empty group: gv = inf, no effect)
@@ -1315,7 +1358,7 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
       // below would hold four times), the window rotated by register moves
       for (int jj = 0; jj < nmax; jj++) {
         const int j = __builtin_amdgcn_readfirstlane(jj);
-        column(j, xA, xB, xC, xD, yA, yB, yC, yD, oA, oB, oC, oD, gA, gB, gC, gD);
+        column(j, xA, xB, xC, xD, yA, yB, yC, yD, oA, oB, oC, oD, gA, gB, gC, gD, hA, hB);
         const int xt = xD;
         xD = xC;
         xC = xB;
@@ -1340,13 +1383,13 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
     } else
     for (int jj = 0; jj < nmax; jj += 4) {
       const int j = __builtin_amdgcn_readfirstlane(jj);  // column index in an SGPR
-      column(j, xA, xB, xC, xD, yA, yB, yC, yD, oA, oB, oC, oD, gA, gB, gC, gD);
+      column(j, xA, xB, xC, xD, yA, yB, yC, yD, oA, oB, oC, oD, gA, gB, gC, gD, hA, hB);
       if (j + 1 < nmax)
-        column(j + 1, xD, xA, xB, xC, yD, yA, yB, yC, oD, oA, oB, oC, gD, gA, gB, gC);
+        column(j + 1, xD, xA, xB, xC, yD, yA, yB, yC, oD, oA, oB, oC, gD, gA, gB, gC, hB, hA);
       if (j + 2 < nmax)
-        column(j + 2, xC, xD, xA, xB, yC, yD, yA, yB, oC, oD, oA, oB, gC, gD, gA, gB);
+        column(j + 2, xC, xD, xA, xB, yC, yD, yA, yB, oC, oD, oA, oB, gC, gD, gA, gB, hA, hB);
       if (j + 3 < nmax)
-        column(j + 3, xB, xC, xD, xA, yB, yC, yD, yA, oB, oC, oD, oA, gB, gC, gD, gA);
+        column(j + 3, xB, xC, xD, xA, yB, yC, yD, yA, oB, oC, oD, oA, gB, gC, gD, gA, hB, hA);
     }
     // find_segments (utils.py:633-644): starts of the optimal segments + the last point
     if (n >= 1) {

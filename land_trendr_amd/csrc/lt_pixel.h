@@ -371,6 +371,46 @@ __host__ __device__ inline double dp_start_bound(double e, double opta, double e
   return dp_start_bound_slack(e, opta, eopt, c, 4.0 * kScreen * SyyAll * (1.0 + 0x1p-49));
 }
 
+// The same exit one start lower, with residuals of neighbouring triples (LT_DP_NEIGHBOUR, default
+// on; 0 compiles the exit above alone). After start i of column j every remaining start i' is
+// <= k = i - 1. The argument above with k in place of i gives, for i' < k,
+//   v(i') >= e(k,j) + max(OPT[k], c),
+// and v(k) = e(k,j) + c + OPT[k] satisfies it too. e(k,j) is not priced yet, but a least-squares
+// residual never falls when points are added, so e(k,j) >= e(T) for every subset T of the points
+// k..j: T = i..j (e(i,j), just priced), and the triples (j-3, j-2, j-1) when k <= j-3 and
+// (j-4, j-3, j-2) when k <= j-4. With E1[t] the closed-form residual of the triple (t-2, t-1, t),
+// which column t prices as its first start of >= 3 points:
+//   LB = max(e(i,j), E1[j-1] (if i <= j-2), E1[j-2] (if i <= j-3)) + max(OPTa[k] - eopt_k, c).
+// Three residuals are involved as before (the reference's e(i',j), the reference's e(i',k-1)
+// inside OPT[k], and one closed-form residual of a subset of 0..j: each within kScreen * SyyAll of
+// the exact one), so the same slack and factor cover the roundings, and the comparison with the
+// upper bound stays strict (ties excluded). A missing triple (t < 2) counts 0, a valid lower bound.
+// The column may end when either bound clears the upper bound: one max of the two sums, then the
+// shared multiply and subtract. eh = the max of the E1 values that apply (0 if none); optk, eoptk
+// = OPTa[k] and its error bound.
+// On noisy series (triple residuals far above c) the optimum is 1- and 2-point segments and a lane
+// goes on to start j-3 only when (j-2, j-1, j) happens to be nearly collinear; the triple one
+// column earlier nearly never is as well, so most second and third starts a wave would price for
+// a few of its lanes go away (tools/dp_lockstep_model.py --neighbour).
+#ifndef LT_DP_NEIGHBOUR
+#define LT_DP_NEIGHBOUR 1
+#endif
+__host__ __device__ inline double dp_start_bound_nb_slack(double e, double opta, double eopt,
+                                                          double eh, double optk, double eoptk,
+                                                          double c, double slack) {
+  const double o = opta - eopt > c ? opta - eopt : c;
+  const double ok = optk - eoptk > c ? optk - eoptk : c;
+  const double en = eh > e ? eh : e;
+  const double s0 = e + o, s1 = en + ok;
+  return (s1 > s0 ? s1 : s0) * (1.0 - 0x1p-49) - slack;
+}
+__host__ __device__ inline double dp_start_bound_nb(double e, double opta, double eopt, double eh,
+                                                    double optk, double eoptk, double c,
+                                                    double SyyAll) {
+  return dp_start_bound_nb_slack(e, opta, eopt, eh, optk, eoptk, c,
+                                 4.0 * kScreen * SyyAll * (1.0 + 0x1p-49));
+}
+
 // Zero-residual starts. The reference prices start i of column j as fl(fl(e + c) + OPT[i])
 // (utils.py:627) with e = 0.0 exactly for 1-2 points (no residuals, utils.py:592-597) and e >= 0
 // the emulated dgelsd residual otherwise. When the segment's exact SSE is 0 (collinear points)
@@ -417,7 +457,9 @@ __host__ __device__ inline void dp_screened(int n, const uint8_t* xs, const doub
                                    double* OPT, uint8_t* arg, int& status) {
   double va[MAXY];
   double SyyAll = 0.0;  // sum of y^2 over the points 0..j
+  double E1a = 0.0, E1b = 0.0;  // E1[j-1], E1[j-2] (dp_start_bound_nb)
   for (int j = 0; j < n; j++) {
+    double e1 = 0.0;
     // pass 1: approximate price of every start, i from j down to 0 (incremental sums)
     double Sy = 0.0, Sxy = 0.0, Syy = 0.0;
     int Sx = 0, Sxx = 0;
@@ -449,8 +491,18 @@ __host__ __device__ inline void dp_screened(int n, const uint8_t* xs, const doub
       vmin = v < vmin ? v : vmin;
       wmax = w > wmax ? w : wmax;
       Hc = v + w < Hc ? v + w : Hc;
+#if LT_DP_NEIGHBOUR
+      if (m == 3) e1 = e;
+      if (m >= 3 && c >= 0.0 && i >= 1) {
+        const double eh = m >= 4 && E1b > E1a ? E1b : E1a;
+        if (dp_start_bound_nb(e, OPT[i], 0.0, eh, OPT[i - 1], 0.0, c, SyyAll) > Hc) break;
+      }
+#else
       if (m >= 3 && c >= 0.0 && dp_start_bound(e, OPT[i], 0.0, c, SyyAll) > Hc) break;
+#endif
     }
+    E1b = E1a;
+    E1a = e1;
     // pass 2: exact price for the starts inside the window, first exact minimum wins
     const double lim = vmin + 2.0 * wmax;
     double best = 0.0;
@@ -500,7 +552,9 @@ __host__ __device__ inline bool dp_lazy(int n, const uint8_t* xs, const double* 
     intdata = intdata && ys[k] == (double)(int)ys[k] && ys[k] >= -32768.0 && ys[k] <= 32767.0;
   const bool zero_ok = c > 0.0;
   double SyyAll = 0.0;  // sum of y^2 over the points 0..j (early exit, as in dp_screened)
+  double E1a = 0.0, E1b = 0.0;  // E1[j-1], E1[j-2] (dp_start_bound_nb)
   for (int j = 0; j < n; j++) {
+    double e1 = 0.0;
     SyyAll += ys[j] * ys[j];
     double Sy = 0.0, Sxy = 0.0, Syy = 0.0;
     int Sx = 0, Sxx = 0;
@@ -587,8 +641,18 @@ __host__ __device__ inline bool dp_lazy(int n, const uint8_t* xs, const double* 
       }
       double Hc = Hi < Ve ? Hi : Ve;
       if (gi >= 0 && gv + gw < Hc) Hc = gv + gw;
+#if LT_DP_NEIGHBOUR
+      if (m == 3) e1 = e;
+      if (m >= 3 && c >= 0.0 && i >= 1) {
+        const double eh = m >= 4 && E1b > E1a ? E1b : E1a;
+        if (dp_start_bound_nb(e, OPTa[i], E[i], eh, OPTa[i - 1], E[i - 1], c, SyyAll) > Hc) break;
+      }
+#else
       if (m >= 3 && c >= 0.0 && dp_start_bound(e, OPTa[i], E[i], c, SyyAll) > Hc) break;
+#endif
     }
+    E1b = E1a;
+    E1a = e1;
     if (gi >= 0) track(gi, gv, gw, gtag + 1);
     const double H = Hi < Ve ? Hi : Ve;  // the exact minimum lies in [min lower bound, H]
     if (Li1 > H) {  // no interval reaches H: the exact candidates decide, bit-exactly

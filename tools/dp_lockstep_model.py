@@ -10,7 +10,11 @@ and the starts of >= 3 points priced before the exit are counted per lane and co
 averages (lane mean vs wave maximum), the distributions, and what deferring every pixel that
 needs more than B starts in some column would leave.
 
-    python tools/dp_lockstep_model.py --config c2 --pixels 6400
+--neighbour D (1 or 2) adds the exit test's neighbouring triples (lt_pixel.h dp_start_bound_nb):
+after start i the starts below also contain the triple (j-3, j-2, j-1) and, from j-3 on, the
+triple (j-4, j-3, j-2), whose closed-form residuals the last D columns priced as their first start.
+
+    python tools/dp_lockstep_model.py --config c2 --pixels 6400 [--neighbour 2]
 """
 import argparse
 import collections
@@ -64,11 +68,14 @@ def series_of(cfg, P):
     return out, c['line_cost']
 
 
-def starts_per_column(x, y, cost):
-    """Starts of >= 3 points the exit test lets through, per column (exact OPT)."""
+def starts_per_column(x, y, cost, depth=0):
+    """Starts of >= 3 points the exit test lets through, per column (exact OPT). depth: the
+    number of earlier columns whose first-triple residual E1 the test also uses (0: the plain
+    test)."""
     n = len(x)
     OPT = np.zeros(n + 1)
     K = np.zeros(n, int)
+    E1 = np.zeros(n)
     syy_all = 0.0
     for j in range(n):
         syy_all += y[j] * y[j]
@@ -93,7 +100,15 @@ def starts_per_column(x, y, cost):
             best = min(best, v)
             if m >= 3:
                 K[j] += 1
-                if (e + max(OPT[i], cost)) * (1 - 2 ** -49) - slack > H:
+                if m == 3:
+                    E1[j] = e
+                s = e + max(OPT[i], cost)
+                if depth and i >= 1:
+                    eh = E1[j - 1] if j >= 3 else 0.0
+                    if depth >= 2 and m >= 4 and j >= 4:
+                        eh = max(eh, E1[j - 2])
+                    s = max(s, max(e, eh) + max(OPT[i - 1], cost))
+                if s * (1 - 2 ** -49) - slack > H:
                     break
         OPT[j + 1] = best
     return K
@@ -120,12 +135,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--config', default='c2')
     ap.add_argument('--pixels', type=int, default=6400)
+    ap.add_argument('--neighbour', type=int, default=0, choices=(0, 1, 2),
+                    help='history depth of the neighbouring-triple exit (0: the plain test)')
     a = ap.parse_args()
     series, cost = series_of(a.config, a.pixels)
-    Ks = [starts_per_column(x, y, cost) for x, y in series]
+    Ks = [starts_per_column(x, y, cost, a.neighbour) for x, y in series]
     wave, lane, cols, hist = lockstep(Ks)
     allk = np.concatenate([k for k in Ks if len(k)])
-    res = {'config': a.config, 'pixels': a.pixels, 'columns': cols,
+    res = {'config': a.config, 'pixels': a.pixels, 'neighbour_depth': a.neighbour, 'columns': cols,
            'wave_starts_per_column': round(wave, 3), 'lane_mean_starts_per_column': round(lane, 3),
            'wave_max_hist': {str(k): v for k, v in sorted(hist.items())},
            'lane_starts_hist': {str(k): int(v) for k, v in
