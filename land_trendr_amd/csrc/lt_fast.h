@@ -109,6 +109,13 @@ __device__ inline void year_row_store(double v, double* a) {
 #else
 #define LT_DP_NB_SPEC 0
 #endif
+// the lazy DP's first triple priced without running sums (lt_pixel.h LT_DP_TRIPLE), in the same
+// kernels: the ones that hold the DP without a spill (DESIGN.md § (d))
+#if LT_DP_TRIPLE && defined(LT_SPEC_NRULES)
+#define LT_DP_TRIPLE_SPEC 1
+#else
+#define LT_DP_TRIPLE_SPEC 0
+#endif
 
 namespace lt {
 
@@ -982,6 +989,14 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
     // planes) spilled more VGPRs than before (DESIGN.md § (d))
     constexpr bool NB = LT_DP_NB_SPEC != 0 && !EXACT && RMAX == 1;
     double hA = 0.0, hB = 0.0;
+    // the first start of >= 3 points of a column, the triple (j-2, j-1, j), priced from the
+    // register window alone (lt_pixel.h dp_triple_sse); the running sums are built only when the
+    // wave goes on to a second start. The same kernels as NB
+    constexpr bool TRI = LT_DP_TRIPLE_SPEC != 0 && !EXACT && RMAX == 1;
+    // TRI: the last column's gap and value difference (x_j - x_{j-1}, y_j - y_{j-1}) kept for the
+    // next column's triple, where they are d2 and b (three registers, no spill)
+    int pd = 0;
+    double pa = 0.0;
     double SyyAll = 0.0;                // sum of y^2 over the points 0..j
     const bool prune = c >= 0.0;
     // zero-residual starts of >= 3 points (lt_pixel.h kZero): integer series of int16 range only
@@ -1159,6 +1174,16 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
       wx0 = L.xn[j][lane];
       wy0 = (double)L.ys[j][lane];
       SyyAll = __builtin_fma(wy0, wy0, SyyAll);
+      // TRI: the last column's gap and difference (cd, ca: d2 and b of this column's triple)
+      // beside this column's (pd, pa: d1 and a), which the next column reads
+      int cd = 0;
+      double ca = 0.0;
+      if constexpr (TRI) {
+        cd = pd;
+        ca = pa;
+        pd = wx0 - wx1;
+        pa = wy0 - wy1;
+      }
       auto add_xy = [&](int xi, double yi) {
         Sx += xi;
         Sxx += xi * xi;
@@ -1200,6 +1225,27 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
         eo = e;
         return e <= ws;  // (zlane applied by the caller: see zmask)
       };
+      // the triple (j-2, j-1, j) priced from the window (TRI), no sums: the same outputs, with the
+      // segment's sum of squares s3 and the numerator n3 (0 exactly when an integer triple is
+      // collinear) for its zero test. (Written out beside price, not shared with it: with
+      // LT_DP_TRIPLE=0 the kernels keep the code they had, instruction for instruction)
+      auto price3 = [&](double o, int tg, double eh, double ok, double wk, double& v, double& hi,
+                        double& lo, double& bnd, double& eo, double& s3, double& n3)
+                        __attribute__((always_inline)) {
+        // (the operations of dp_triple_sse, its differences taken from the registers above)
+        s3 = __builtin_fma(wy2, wy2, __builtin_fma(wy1, wy1, wy0 * wy0));
+        const double e = dp_triple_sse_diff(pd, cd, pa, ca, n3);
+        v = (e + c) + o;
+        const double wopt = (tg >= 0 && tg < 256) ? 0.0 : Emax;
+        const double ws = kScreen * s3;
+        const double w = __builtin_fma(0x1p-50, __builtin_fabs(v), ws + wopt);
+        hi = v + w;
+        lo = v - w;
+        if constexpr (NB) bnd = dp_start_bound_nb_slack(e, o, wopt, eh, ok, wk, c, slack);
+        else bnd = dp_start_bound_slack(e, o, wopt, c, slack);
+        eo = e;
+        return e <= ws;
+      };
       // exactly collinear with a residual that rounds away (lt_pixel.h kZero, sse_exact_zero), on
       // sums of integer data (exact binary64 integers)
       auto zero_test = [&](int m, int sx, int sxx, double sy, double sxy, double syy)
@@ -1221,9 +1267,12 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
         }
         track(i, v, hi, lo, -1);
       };
-      // the 1- and 2-point starts (priced above) only add their points to the sums
-      add_xy(wx0, wy0);
-      if (j >= 1) add_xy(wx1, wy1);
+      // the 1- and 2-point starts (priced above) only add their points to the sums (TRI: the sums
+      // wait until a second start of >= 3 points is priced, below)
+      if constexpr (!TRI) {
+        add_xy(wx0, wy0);
+        if (j >= 1) add_xy(wx1, wy1);
+      }
       // an upper bound on the column minimum so far (it only decreases as starts are added). A
       // start whose lower end lies above it can change no decision: it is neither the smallest
       // upper end nor among the lower ends at or below the final minimum bound H
@@ -1254,6 +1303,28 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
         }
         return bnd;
       };
+      // start j-2, the triple of the window (TRI), the same way without sums: collinear integer
+      // points have n3 == 0 (lt_pixel.h dp_triple_sse), under the same condition on the
+      // rounded-away residual as zero_test. (Only the analyze stage's kernels: no candidates of
+      // exact decisions to collect)
+      auto first_start = [&](double o, int tg, double eh, double ok, double wk, double& eo)
+                             __attribute__((always_inline)) {
+        static_assert(!(TRI && EXACT), "first_start collects no candidates for the resolve stage");
+        const int i = j - 2;
+        double v, hi, lo, bnd, s3, n3;
+        const bool nz = price3(o, tg, eh, ok, wk, v, hi, lo, bnd, eo, s3, n3);
+        if (__ballot(lo <= upper())) {
+          if (__ballot(nz) & zmask) {  // rare: exactly collinear candidates
+            const bool zr = zlane && nz && zero_bound(wx0) * s3 < 0x1p-54 * c && n3 == 0.0;
+            if (__ballot(zr)) {
+              offer(i, o, tg, v, hi, lo, zr);
+              return bnd;
+            }
+          }
+          track(i, v, hi, lo, -1);
+        }
+        return bnd;
+      };
       // early exit (dp_start_bound): once no start below i can reach an upper bound on the column
       // minimum in any lane, the column is complete; a start priced past that point lies above the
       // bound, so tracking it changes no decision. The starts go one at a time, each with its own
@@ -1263,29 +1334,8 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
       };
       bool more = j >= 2;  // wave-uniform
       double onext = 0.0, hmax = 0.0;
-      if (more) {  // starts j-2 and j-3 from the register window
-        add_xy(wx2, wy2);
-        // the start below, j-3, contains the triple (j-3, j-2, j-1): E1[j-1]. (j == 2: no start
-        // below; the slot of OPTa[j-3] holds 0 then, a bound no larger than the plain one)
-        double e1;
-        more = !leave(one_start(j - 2, opt_jm2, tg_jm2, h1, opt_jm3, Emax, e1));
-        if constexpr (NB) {  // E1[j] over E1[j-2]
-          hmax = __builtin_fmax(h1, h2);
-          h2 = e1;
-        }
-        if (j >= 3 && more) {
-          // OPTa[j-4], the first value the loop below reads, one start ahead: start j-4 and every
-          // lower one contain both neighbouring triples
-          if constexpr (NB) {
-            if (j >= 4) onext = OPTa[j - 4];
-          }
-          add_xy(wx3, wy3);
-          double eo;
-          more = !leave(one_start(j - 3, opt_jm3, tg_jm3, hmax, onext, Emax, eo));
-        }
-        more = more && j >= 3;
-      }
-      if (more) {  // the rest from LDS / private memory
+      // the starts below j-3, from LDS / private memory
+      auto rest = [&]() __attribute__((always_inline)) {
         // the start index in an SGPR through the loop (a VGPR counter cost a VALU decrement and
         // a readfirstlane per start)
         for (int i = __builtin_amdgcn_readfirstlane(j - 4); i >= 0;
@@ -1300,6 +1350,59 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
           } else
           // tags are kept in the window only: a start from private memory is exact or not
           if (leave(one_start(i, OPTa[i], ((exact >> i) & 1) ? 0 : -1, 0.0, 0.0, 0.0, eo))) break;
+        }
+      };
+      if (more) {  // starts j-2 and j-3 from the register window
+        if constexpr (!TRI) add_xy(wx2, wy2);
+        // the start below, j-3, contains the triple (j-3, j-2, j-1): E1[j-1]. (j == 2: no start
+        // below; the slot of OPTa[j-3] holds 0 then, a bound no larger than the plain one)
+        double e1;
+        if constexpr (TRI) more = !leave(first_start(opt_jm2, tg_jm2, h1, opt_jm3, Emax, e1));
+        else more = !leave(one_start(j - 2, opt_jm2, tg_jm2, h1, opt_jm3, Emax, e1));
+        if constexpr (NB) {  // E1[j] over E1[j-2]
+          hmax = __builtin_fmax(h1, h2);
+          h2 = e1;
+        }
+        if (j >= 3 && more) {
+          // OPTa[j-4], the first value the loop below reads, one start ahead: start j-4 and every
+          // lower one contain both neighbouring triples
+          if constexpr (NB) {
+            if (j >= 4) onext = OPTa[j - 4];
+          }
+          if constexpr (TRI) {  // the sums of the triple, in the order they always took
+            add_xy(wx0, wy0);
+            add_xy(wx1, wy1);
+            add_xy(wx2, wy2);
+          }
+          add_xy(wx3, wy3);
+          double eo;
+          more = !leave(one_start(j - 3, opt_jm3, tg_jm3, hmax, onext, Emax, eo));
+          // TRI: the remaining starts inside this branch, the only place the sums exist (after
+          // it they would be merged with the zeros of the columns that never built them:
+          // register moves in every column)
+          if constexpr (TRI) {
+            if (more) rest();
+          }
+        }
+        more = more && j >= 3;
+      }
+      if constexpr (!TRI) {
+        // (the loop of rest, written out: called through the lambda the registers come out
+        // numbered differently, and with LT_DP_TRIPLE=0 the kernels keep the code they had)
+        if (more) {
+          for (int i = __builtin_amdgcn_readfirstlane(j - 4); i >= 0;
+               i = __builtin_amdgcn_readfirstlane(i - 1)) {
+            add_xy(L.xn[i][lane], (double)L.ys[i][lane]);
+            double eo;
+            if constexpr (NB) {
+              const double o = onext;
+              onext = OPTa[i >= 1 ? i - 1 : 0];
+              if (leave(one_start(i, o, ((exact >> i) & 1) ? 0 : -1, hmax, onext, Emax, eo)))
+                break;
+            } else if (leave(one_start(i, OPTa[i], ((exact >> i) & 1) ? 0 : -1, 0.0, 0.0, 0.0,
+                                       eo)))
+              break;
+          }
         }
       }
       // the group's best enters the trackers (an empty group: gv = inf, no effect)

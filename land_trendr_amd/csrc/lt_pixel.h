@@ -411,6 +411,59 @@ __host__ __device__ inline double dp_start_bound_nb(double e, double opta, doubl
                                  4.0 * kScreen * SyyAll * (1.0 + 0x1p-49));
 }
 
+// The first start of >= 3 points of a column, the triple (j-2, j-1, j), priced without running
+// sums (LT_DP_TRIPLE, default on; 0 prices it from the sums like every other start). With the
+// gaps d1 = x_j - x_{j-1}, d2 = x_{j-1} - x_{j-2} and the point j-1 as origin, the least-squares
+// residual of three points is the squared second difference over the squared norm of its weights:
+//   N   = d2 (y_j - y_{j-1}) - d1 (y_{j-1} - y_{j-2})
+//   SSE = N^2 / (d2^2 + (d1 + d2)^2 + d1^2) = N^2 / (2 (d1^2 + d1 d2 + d2^2))
+// (N = w . y with w = (d2, -(d1 + d2), d1) orthogonal to (1, 1, 1) and to x: the residual space of
+// three points has dimension one, so SSE = (w . y)^2 / |w|^2).
+// Integer series of int16 range, year offsets <= 255 (d1 + d2 <= 255): the differences are below
+// 2^17 in magnitude, each product below 2^25, N an exact integer below 2^26 and N^2 exact below
+// 2^52; the denominator is an exact integer below 2^18. Only the reciprocal (relative error e_r,
+// v_rcp_f64 and one Newton step: profiles/r05_rcp_check.json, doubled as in
+// tests/test_screening_bounds.py) and the product round:
+//   |e - SSE| <= (e_r + 2u) SSE <= 2^-47.6 Syy      (SSE <= Syy, u = 2^-53),
+// and N == 0 exactly when the three points are collinear (the zero test of such a start).
+// Binary32 / binary64 series take the same form (one code path; the series type is an instance's,
+// integer values a lane's). With Y = max |y| of the three points (Y^2 <= Syy) and g = d1 + d2,
+// the two differences carry at most 2uY each, the product d1 (y_{j-1} - y_{j-2}) and the fma one
+// rounding each of a term below 2gY: |dN| <= 6.1 u g Y against |N| <= 2gY, so
+// |d(N^2)| <= 24.5 u g^2 Y^2, and the denominator is at least 1.5 g^2 (d1 = d2):
+//   |e - SSE| <= 16.4 u Y^2 + (e_r + 2u) SSE <= 2^-47 Syy.
+// The cancellation in N costs nothing relative to Syy, because the denominator is of the order of
+// the weights' own norm. Either way the error is far inside kScreen Syy = 2^-30 Syy, the emulated
+// dgelsd residual's own 2^-50 Syy included (tests/test_dp_triple.py evaluates both).
+// syy receives the sum of squares of the three values, accumulated in the order the running sums
+// take (points j, j-1, j-2), n the numerator N.
+#ifndef LT_DP_TRIPLE
+#define LT_DP_TRIPLE 1
+#endif
+// (from the two gaps and the two value differences a = y_j - y_{j-1}, b = y_{j-1} - y_{j-2})
+__host__ __device__ inline double dp_triple_sse_diff(int d1, int d2, double a, double b,
+                                                     double& n) {
+  n = __builtin_fma((double)d2, a, -((double)d1 * b));
+#ifdef __HIP_DEVICE_COMPILE__
+  // (factors below 2^24: two full-rate 24-bit multiplies, as dmul24 in lt_fast.h)
+  const unsigned u1 = (unsigned)d1, u2 = (unsigned)d2;
+  const double den = (double)((__umul24(u1, u1 + u2) + __umul24(u2, u2)) << 1);
+  double r = __builtin_amdgcn_rcp(den);
+  r = __builtin_fma(r, __builtin_fma(-den, r, 1.0), r);
+  return __builtin_fmax((n * n) * r, 0.0);
+#else
+  const double den = (double)(2 * (d1 * (d1 + d2) + d2 * d2));
+  const double e = n * n / den;
+  return e < 0.0 ? 0.0 : e;
+#endif
+}
+// (from the three window values: y0 = y_j, y1 = y_{j-1}, y2 = y_{j-2})
+__host__ __device__ inline double dp_triple_sse(int d1, int d2, double y0, double y1, double y2,
+                                                double& syy, double& n) {
+  syy = __builtin_fma(y2, y2, __builtin_fma(y1, y1, y0 * y0));
+  return dp_triple_sse_diff(d1, d2, y0 - y1, y1 - y2, n);
+}
+
 // Zero-residual starts. The reference prices start i of column j as fl(fl(e + c) + OPT[i])
 // (utils.py:627) with e = 0.0 exactly for 1-2 points (no residuals, utils.py:592-597) and e >= 0
 // the emulated dgelsd residual otherwise. When the segment's exact SSE is 0 (collinear points)
@@ -484,6 +537,13 @@ __host__ __device__ inline void dp_screened(int n, const uint8_t* xs, const doub
         e = (t1 - N1 * N1 / D) / md;
         if (e < 0.0) e = 0.0;
         w = kScreen * Syy;
+#if LT_DP_TRIPLE
+        if (m == 3) {  // the triple (j-2, j-1, j): dp_triple_sse
+          double s3, n3;
+          e = dp_triple_sse(xs[j] - xs[j - 1], xs[j - 1] - xs[i], ys[j], ys[j - 1], ys[i], s3, n3);
+          w = kScreen * s3;
+        }
+#endif
       }
       const double v = (e + c) + OPT[i];
       w += 0x1p-50 * __builtin_fabs(v);
@@ -605,8 +665,17 @@ __host__ __device__ inline bool dp_lazy(int n, const uint8_t* xs, const double* 
         e = (t1 - N1 * N1 / D) / md;
         if (e < 0.0) e = 0.0;
         ws = kScreen * Syy;
-        if (zero_ok && intdata && e <= ws && zero_bound(xs[j]) * Syy < 0x1p-54 * c &&
-            sse_exact_zero(t1, D, N1)) {
+        bool z0 = false;
+#if LT_DP_TRIPLE
+        if (m == 3) {  // the triple (j-2, j-1, j): dp_triple_sse, collinear when its N is 0
+          double s3, n3;
+          e = dp_triple_sse(xs[j] - xs[j - 1], xs[j - 1] - xs[i], ys[j], ys[j - 1], ys[i], s3, n3);
+          ws = kScreen * s3;
+          z0 = n3 == 0.0;
+        } else
+#endif
+          z0 = sse_exact_zero(t1, D, N1);
+        if (zero_ok && intdata && e <= ws && zero_bound(xs[j]) * Syy < 0x1p-54 * c && z0) {
           zr = true;
           e = 0.0;
           ws = 0.0;
