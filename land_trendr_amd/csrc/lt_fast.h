@@ -27,51 +27,13 @@
 #ifndef LT_RESOLVE_PRIV_MAXY
 #define LT_RESOLVE_PRIV_MAXY 48
 #endif
-// the resolve stage's DP: 1 = the exact-OPT DP over every column (the default), 0 = the lazy DP
-// with every ambiguous column decided exactly where it arises (c2 resolve 0.63 vs 0.44 ms per
-// launch, 2528 vs 2584 Mpx/s, profiles/r04_run13: the stage is latency-bound, not LAPACK-bound)
-#ifndef LT_RESOLVE_FULL
-#define LT_RESOLVE_FULL 1
+// switches of variants that were measured, rejected and removed: a build that still
+// names one would time the default code under the variant's label
+#if defined(LT_RESOLVE_FULL) || defined(LT_RESOLVE_GROUP) || defined(LT_AB_NO_YEAR_STORES) || \
+    defined(LT_AB_NO_FITS) || defined(LT_AB_YEAR_SINK) || defined(LT_YEAR_NT) ||               \
+    defined(LT_YEAR_STORE_MODE)
+#error "LT_RESOLVE_FULL, LT_RESOLVE_GROUP, LT_AB_NO_YEAR_STORES, LT_AB_NO_FITS, LT_AB_YEAR_SINK, LT_YEAR_NT and LT_YEAR_STORE_MODE were removed: commit 286151f is the last that has them"
 #endif
-// timing-only attribution builds (wrong outputs; A/B runs through LT_JIT_DEFINES):
-// LT_AB_NO_YEAR_STORES = 1 drops the year-major loop's per-year plane stores, 2 also the winner
-// pick's val_raw / winner rows; LT_AB_NO_FITS = 1 drops the year-major loop's emulated fits
-#ifndef LT_AB_NO_YEAR_STORES
-#define LT_AB_NO_YEAR_STORES 0
-#endif
-#ifndef LT_AB_NO_FITS
-#define LT_AB_NO_FITS 0
-#endif
-// LT_AB_YEAR_SINK = 1: the year-major loop's plane stores all go to the pixel's year-0 row (the
-// same instructions and bytes leave the CUs, ~1/Y of them reach HBM), nontemporal; 2: the same
-// with ordinary stores (the rows then stay in L2)
-#ifndef LT_AB_YEAR_SINK
-#define LT_AB_YEAR_SINK 0
-#endif
-// the year-major loop's binary64 plane stores: 1 nontemporal (the default), 0 plain
-#ifndef LT_YEAR_NT
-#define LT_YEAR_NT 1
-#endif
-// cache policy of the per-year binary64 row stores (year-major planes and val_raw): 0 the
-// compiler's nontemporal store (nt: the line stays in the XCD's L2), 1 sc1 (write-through, the
-// line dropped from L2: MI355X_MICROARCH.md, store flavours), 2 sc0 sc1, 3 nt sc1
-#ifndef LT_YEAR_STORE_MODE
-#define LT_YEAR_STORE_MODE 0
-#endif
-
-namespace lt {
-__device__ inline void year_row_store(double v, double* a) {
-#if LT_YEAR_STORE_MODE == 1
-  asm volatile("global_store_dwordx2 %0, %1, off sc1" ::"v"(a), "v"(v) : "memory");
-#elif LT_YEAR_STORE_MODE == 2
-  asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1" ::"v"(a), "v"(v) : "memory");
-#elif LT_YEAR_STORE_MODE == 3
-  asm volatile("global_store_dwordx2 %0, %1, off sc1 nt" ::"v"(a), "v"(v) : "memory");
-#else
-  __builtin_nontemporal_store(v, a);
-#endif
-}
-}  // namespace lt
 // labels-only launches of up to this many rules take the certified path (closed-form fits, the
 // emulated ones only around the rules' candidates); more rules keep one emulated fit per vertex
 #ifndef LT_CERT_RULES
@@ -191,9 +153,9 @@ __device__ inline int lsq_fit_lockstep(bool act, int m, GX X, GY Y,
 // VT: storage type of the series. The analyze stage stores int16 (an int16 index raster), binary32
 // (other index types: pixels whose values are not exact in binary32 are sent to the resolve stage)
 // or binary64 (binary64 values, up to 4 rules); the resolve stage the same, or binary64.
-// AGLDS: the DP argmin of each column in LDS (resolve stage: its registers are spent on the exact
-// DP) or, when false, in the lane's registers / private memory (analyze stage: 2 KB less LDS per
-// wave, 15 instead of 12 resident waves per CU)
+// AGLDS: the DP argmin of each column in LDS (resolve stage: the exact-OPT DP's OPT takes its
+// registers / private memory) or, when false, in the lane's registers / private memory (analyze
+// stage, the lazy DP: 2 KB less LDS per wave, 15 instead of 12 resident waves per CU)
 template <int MAXY, class VT, bool AGLDS>
 struct WaveLds {
   VT ys[MAXY][64];       // present values (t), compacted in place to non-spike (k)
@@ -205,10 +167,8 @@ struct WaveLds {
 // EXACT = false (analyze stage): the lazy DP; returns kDeferExact when the pixel's optimal path
 // crosses an ambiguous DP column, kDeferWide when its values are not exact in binary32 (the
 // resolve stage redoes them with binary32 / binary64 LDS series), else kDone.
-// EXACT = true (resolve stage): the same lazy DP, but a column its intervals cannot decide is
-// decided on the spot with the emulated LAPACK residuals of the candidates (and of the links of
-// their optimal prefixes whose values are not yet exact); always kDone. (LT_RESOLVE_FULL: the
-// exact-OPT DP over every column instead.)
+// EXACT = true (resolve stage): the exact-OPT DP, every column decided with the emulated LAPACK
+// residuals of the starts its closed-form intervals leave in question; always kDone.
 enum { kDone = 0, kDeferExact = 1, kDeferWide = 2 };
 
 // Phase probe of analyze_fast: probe.mark(k) is called by every lane at the end of phase k
@@ -529,7 +489,7 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
       }
       if (!live) continue;
       const int64_t q = (int64_t)y * os + p;
-      if (LT_OUTF(out, winner) && LT_AB_NO_YEAR_STORES < 2)
+      if (LT_OUTF(out, winner))
         __builtin_nontemporal_store((int16_t)best[u], LT_OUTF(out, winner) + q);
       if (best[u] >= 0) {
         if ((S.feb29_mask >> y) & 1) status |= LT_ST_FEB29;
@@ -554,9 +514,9 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
         }
         pres |= 1ull << y;
         T++;
-        if (LT_OUTF(out, val_raw) && LT_AB_NO_YEAR_STORES < 2)
-          year_row_store(v, LT_OUTF(out, val_raw) + q);
-      } else if (LT_OUTF(out, val_raw) && LT_AB_NO_YEAR_STORES < 2) {  // the other per-year planes: the year-major output loop
+        if (LT_OUTF(out, val_raw))
+          __builtin_nontemporal_store(v, LT_OUTF(out, val_raw) + q);
+      } else if (LT_OUTF(out, val_raw)) {  // the other per-year planes: the year-major output loop
         __builtin_nontemporal_store(nan, LT_OUTF(out, val_raw) + q);
       }
     }
@@ -764,7 +724,7 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
     if constexpr (EXACT) return L.ag[j][lane];
     else return AG[j];
   };
-  if constexpr (EXACT && LT_RESOLVE_FULL != 0) {
+  if constexpr (EXACT) {
     if constexpr (MAXY <= LT_RESOLVE_PRIV_MAXY) {
       // ---- exact-OPT DP: closed-form intervals, then the emulated LAPACK residual for every
       // start whose interval reaches the column's smallest upper bound; first exact minimum ----
@@ -982,17 +942,17 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
     // the exit test's neighbouring triples (lt_pixel.h dp_start_bound_nb): E1[j-1] and E1[j-2],
     // the closed-form residual the last two columns priced as their first start; column j writes
     // E1[j] over E1[j-2], so the two slots alternate with the unrolled columns (no copies).
-    // The analyze stage's one-rule kernels specialised for a configuration only (LT_DP_NB_SPEC):
-    // they hold the DP in 128 VGPRs without a spill. The resolve stage keeps the exit it had, and
-    // so do the kernels that spill already (several rules, or rules and line cost read from the
-    // launch): every form of the history tried there (binary64 or binary32 registers, LDS
-    // planes) spilled more VGPRs than before (DESIGN.md § (d))
-    constexpr bool NB = LT_DP_NB_SPEC != 0 && !EXACT && RMAX == 1;
+    // The one-rule kernels specialised for a configuration only (LT_DP_NB_SPEC): they hold the DP
+    // in 128 VGPRs without a spill. The kernels that spill already (several rules, or rules and
+    // line cost read from the launch) keep the exit they had: every form of the history tried
+    // there (binary64 or binary32 registers, LDS planes) spilled more VGPRs than before
+    // (DESIGN.md § (d))
+    constexpr bool NB = LT_DP_NB_SPEC != 0 && RMAX == 1;
     double hA = 0.0, hB = 0.0;
     // the first start of >= 3 points of a column, the triple (j-2, j-1, j), priced from the
     // register window alone (lt_pixel.h dp_triple_sse); the running sums are built only when the
     // wave goes on to a second start. The same kernels as NB
-    constexpr bool TRI = LT_DP_TRIPLE_SPEC != 0 && !EXACT && RMAX == 1;
+    constexpr bool TRI = LT_DP_TRIPLE_SPEC != 0 && RMAX == 1;
     // TRI: the last column's gap and value difference (x_j - x_{j-1}, y_j - y_{j-1}) kept for the
     // next column's triple, where they are d2 and b (three registers, no spill)
     int pd = 0;
@@ -1004,83 +964,6 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
     const bool zlane = zok && intdata;
     const uint64_t zmask = __ballot(zlane);
     uint64_t amb = 0;
-    // resolve stage: the exact decision of column j for the lanes xr (see column below). One
-    // lockstep loop of emulated residuals: per lane first the links k (OPTa[k] = fl(fl(e(a, k-1) +
-    // c) + OPTa[a]), a = argmin of column k-1) that the candidates' OPT values need, in increasing
-    // k, then the candidates in increasing start order (strict "<": the first minimum)
-    auto resolve_column = [&](const int j, const bool xr, const double H, uint64_t cs,
-                              const double opt_j, const int tg_j, const double opt_jm1,
-                              const int tg_jm1, int& a, double& vnew) {
-      // the 1- and 2-point starts j, j-1 (residual 0), when their interval reaches H
-      {
-        const double v0 = c + opt_j;
-        const double w0 = tg_j < 256 ? 0.0 : __builtin_fma(0x1p-50, __builtin_fabs(v0), Emax);
-        if (!(v0 - w0 > H)) cs |= 1ull << j;
-        if (j >= 1) {
-          const double v1s = c + opt_jm1;
-          const double w1 =
-              tg_jm1 < 256 ? 0.0 : __builtin_fma(0x1p-50, __builtin_fabs(v1s), Emax);
-          if (!(v1s - w1 > H)) cs |= 1ull << (j - 1);
-        }
-      }
-      if (!xr) cs = 0;
-      uint64_t need = cs & ~exact;  // OPTa entries to make exact, with their prefixes' links
-      {
-        const int top = wave_max(need ? 63 - __builtin_clzll(need) : 0);
-        for (int kk = top; kk >= 1; kk--) {
-          const int k = __builtin_amdgcn_readfirstlane(kk);
-          if ((need >> k) & 1) {
-            const int b = L.ag[k - 1][lane];
-            if (!((exact >> b) & 1)) need |= 1ull << b;
-          }
-        }
-      }
-      const int steps = wave_max(__builtin_popcountll(need) + __builtin_popcountll(cs));
-      double best = inf;
-      int bi = 0;
-      for (int r = 0; r < steps; r++) {
-        const bool link = need != 0;
-        const bool act = link || cs != 0;
-        int i = 0, m = 0;  // the segment: points i .. i+m-1
-        int k = 0;
-        if (link) {
-          k = __builtin_ctzll(need);
-          need &= need - 1;
-          i = L.ag[k - 1][lane];
-          m = k - i;
-        } else if (act) {
-          i = __builtin_ctzll(cs);
-          cs &= cs - 1;
-          m = j - i + 1;
-        }
-        const bool ls = act && m >= 3;
-        double e = 0.0;
-        if (__ballot(ls)) {
-          double sm, sb, ssr;
-          const int rc = lsq_lockstep(
-              ls, m, [&](int q) { return (int)L.xn[i + q][lane]; },
-              [&](int q) { return (double)L.ys[i + q][lane]; }, xtab, false, true, sm, sb, ssr);
-          if (ls) {
-            if (rc < 0) status |= LT_ST_NUMERIC;
-            e = ssr;
-          }
-        }
-        if (act) {
-          const double v = (e + c) + OPTa[i];  // per-lane index: exact by now
-          if (link) {
-            OPTa[k] = v;
-            exact |= 1ull << k;
-          } else if (v < best) {
-            best = v;
-            bi = i;
-          }
-        }
-      }
-      if (xr) {
-        a = bi;
-        vnew = best;
-      }
-    };
     // column j: wx0 receives point j (its slot held point j-4); wx1..wx3 hold points j-1..j-3;
     // opt_j..opt_jm3 hold OPTa[j..j-3] (tags tg_*), and OPTa[j+1] is written over opt_jm3
     auto column = [&](const int j, int& wx0, int& wx1, int& wx2, int& wx3, double& wy0,
@@ -1100,7 +983,6 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
       // current upper bound without recomputing it per start
       double U = inf;
       int ie = 0, i1 = 0, iL = -1, n1 = -1, gi = -1, gt = 0;
-      uint64_t cand = 0;  // resolve stage: the >= 3-point starts an exact decision prices
       // (the bounds Hi, L1, L2 are only compared: v_min_f64 instead of a select pair; the values
       // that become OPTa, v1 and Ve, are selected)
       auto track = [&](int i, double v, double hi, double lo, int nt) __attribute__((always_inline)) {
@@ -1273,25 +1155,18 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
         add_xy(wx0, wy0);
         if (j >= 1) add_xy(wx1, wy1);
       }
-      // an upper bound on the column minimum so far (it only decreases as starts are added). A
-      // start whose lower end lies above it can change no decision: it is neither the smallest
-      // upper end nor among the lower ends at or below the final minimum bound H
-      auto upper = [&]() __attribute__((always_inline)) { return U; };
-      // start i (>= 3 points, its point already in the sums): priced, offered to the trackers when
-      // its lower end reaches the column's current upper bound (else it can change no decision),
-      // its early-exit bound returned
+      // U is an upper bound on the column minimum so far (it only decreases as starts are added).
+      // A start whose lower end lies above it can change no decision: it is neither the smallest
+      // upper end nor among the lower ends at or below the final minimum bound H.
+      // Start i (>= 3 points, its point already in the sums): priced, offered to the trackers when
+      // its lower end reaches U (else it can change no decision), its early-exit bound returned
       auto one_start = [&](int i, double o, int tg, double eh, double ok, double wk, double& eo)
                            __attribute__((always_inline)) {
         double v, hi, lo, bnd;
         const bool nz = price(i, o, tg, eh, ok, wk, v, hi, lo, bnd, eo);
-        // resolve stage: every start whose interval reaches the column's current upper bound (a
-        // NaN bound included) is a candidate of an exact decision
-        if constexpr (EXACT) {
-          if (!(lo > upper())) cand |= 1ull << i;
-        }
         // (each ballot of a single compare, masked by a ballot taken once: a ballot of a compound
         // condition is materialised in a VGPR as 0 / 1 and compared again, two VALU per test)
-        if (__ballot(lo <= upper())) {
+        if (__ballot(lo <= U)) {
           if (__ballot(nz) & zmask) {  // rare: exactly collinear candidates
             const bool zr = zlane && nz && zero_test(j - i + 1, Sx, Sxx, Sy, Sxy, Syy);
             if (__ballot(zr)) {
@@ -1305,15 +1180,13 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
       };
       // start j-2, the triple of the window (TRI), the same way without sums: collinear integer
       // points have n3 == 0 (lt_pixel.h dp_triple_sse), under the same condition on the
-      // rounded-away residual as zero_test. (Only the analyze stage's kernels: no candidates of
-      // exact decisions to collect)
+      // rounded-away residual as zero_test
       auto first_start = [&](double o, int tg, double eh, double ok, double wk, double& eo)
                              __attribute__((always_inline)) {
-        static_assert(!(TRI && EXACT), "first_start collects no candidates for the resolve stage");
         const int i = j - 2;
         double v, hi, lo, bnd, s3, n3;
         const bool nz = price3(o, tg, eh, ok, wk, v, hi, lo, bnd, eo, s3, n3);
-        if (__ballot(lo <= upper())) {
+        if (__ballot(lo <= U)) {
           if (__ballot(nz) & zmask) {  // rare: exactly collinear candidates
             const bool zr = zlane && nz && zero_bound(wx0) * s3 < 0x1p-54 * c && n3 == 0.0;
             if (__ballot(zr)) {
@@ -1330,7 +1203,7 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
       // bound, so tracking it changes no decision. The starts go one at a time, each with its own
       // exit test (pricing two per exit test: 2115 vs 2231 Mpx/s on c2, profiles/r02_ab_dp)
       auto leave = [&](double bnd) __attribute__((always_inline)) {
-        return prune && (__ballot(!(bnd > upper())) & colmask) == 0;
+        return prune && (__ballot(!(bnd > U)) & colmask) == 0;
       };
       bool more = j >= 2;  // wave-uniform
       double onext = 0.0, hmax = 0.0;
@@ -1413,8 +1286,8 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
       const double H = __builtin_fmin(Hi, Ve);  // the exact minimum lies in [min(L1, Ve), H]
       int a, tnew;
       double vnew, enew = 0.0;
-      bool xres = false;  // resolve stage: this lane decides the column exactly
-      if (L1 > H) {  // no inexact interval reaches H: the exact candidates decide
+      const bool certain = L1 > H;  // no inexact interval reaches H: the exact candidates decide
+      if (certain) {
         a = ie;
         vnew = Ve;
         tnew = 0;
@@ -1425,27 +1298,13 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
         tnew = n1 >= 0 ? n1 : (j + 1) << 8;
         // its half-width, rounded up: Hi = fl(v1 + w1) >= v1 + w1 - ulp(Hi) / 2
         enew = __builtin_fma(Hi - v1, 1.0 + 0x1p-50, 0x1p-50 * __builtin_fabs(Hi));
-      } else {
-        if constexpr (EXACT) xres = col;
-        else if (col) amb |= 1ull << j;
+      } else {  // ambiguous: the pixel goes to the resolve stage if its optimal path comes here
+        if (col) amb |= 1ull << j;
         a = v1 <= Ve ? i1 : ie;
         vnew = v1 <= Ve ? v1 : Ve;
         tnew = (j + 1) << 8;
         const double Lo = __builtin_fmin(L1, Ve);
         enew = (H - Lo) * (1.0 + 0x1p-40) + 0x1p-50 * __builtin_fabs(vnew);
-      }
-      if constexpr (EXACT) {
-        // resolve stage: an ambiguous column is decided exactly here, so no interval widens
-        // Emax and the next columns keep their certified decisions. The candidates are the
-        // starts whose interval reaches H; each is worth fl(fl(e + c) + OPT[i]) with e the
-        // emulated LAPACK residual (0 for 1-2 points) and OPT[i] the reference value: where OPTa[i]
-        // is not exact yet, the links of its optimal prefix (argmins of decided columns, each
-        // the reference's) are priced first, in increasing order, each made exact once.
-        if (__ballot(xres)) resolve_column(j, xres, H, cand, opt_j, tg_j, opt_jm1, tg_jm1, a, vnew);
-        if (xres) {
-          tnew = 0;
-          enew = 0.0;
-        }
       }
       if (col) {
         ag_set(j, a);
@@ -1456,34 +1315,6 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
         tg_jm3 = tnew;
       }
     };
-    if constexpr (EXACT) {
-      // resolve stage: one column per iteration (its exact decisions are code the unrolled loop
-      // below would hold four times), the window rotated by register moves
-      for (int jj = 0; jj < nmax; jj++) {
-        const int j = __builtin_amdgcn_readfirstlane(jj);
-        column(j, xA, xB, xC, xD, yA, yB, yC, yD, oA, oB, oC, oD, gA, gB, gC, gD, hA, hB);
-        const int xt = xD;
-        xD = xC;
-        xC = xB;
-        xB = xA;
-        xA = xt;
-        const double yt = yD;
-        yD = yC;
-        yC = yB;
-        yB = yA;
-        yA = yt;
-        const double ot = oD;
-        oD = oC;
-        oC = oB;
-        oB = oA;
-        oA = ot;
-        const int gt = gD;
-        gD = gC;
-        gC = gB;
-        gB = gA;
-        gA = gt;
-      }
-    } else
     for (int jj = 0; jj < nmax; jj += 4) {
       const int j = __builtin_amdgcn_readfirstlane(jj);  // column index in an SGPR
       column(j, xA, xB, xC, xD, yA, yB, yC, yD, oA, oB, oC, oD, gA, gB, gC, gD, hA, hB);
@@ -1643,17 +1474,12 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
     // (16-byte stores of pixel pairs from the even lanes, the odd lane's value moved over by DPP:
     // c5 1083-1092 vs 1260 Mpx/s, profiles/r04_run19)
     auto store_row = [&](int yy, const Row& r) __attribute__((always_inline)) {
-      const int64_t o = LT_AB_YEAR_SINK ? p : (int64_t)yy * os + p;
+      const int64_t o = (int64_t)yy * os + p;
       // write-once planes: nontemporal stores (same-box c5 A/B: 1012 vs 896-925 Mpx/s). When
       // the year is present in every emitting lane (always, without a cloud mask) the values
       // are stored as they are: no NaN select pair per plane
       auto put = [&](double* plane, double v) __attribute__((always_inline)) {
-        if (plane && !LT_AB_NO_YEAR_STORES) {
-          if (LT_AB_YEAR_SINK == 2 || !LT_YEAR_NT)
-            plane[o] = v;
-          else
-            year_row_store(v, plane + o);
-        }
+        if (plane) __builtin_nontemporal_store(v, plane + o);
       };
       if (r.uni) {
         put(LT_OUTF(out, val_fit), r.fv);
@@ -1677,7 +1503,7 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
       const bool nextfit = isv && after != 0;
       double sm = 0.0, sbv = 0.0;
       bool fitnow = false;
-      if (__ballot(nextfit && !have_n) && !LT_AB_NO_FITS) {
+      if (__ballot(nextfit && !have_n)) {
         const uint64_t fnext = frem & (frem - 1);
         fitnow = fnext != 0 && (!have_n || nextfit);
         const int kbase = fitnow ? __builtin_ctzll(frem) : 0;

@@ -356,7 +356,8 @@ inline std::string source(const lt_index_prog& P, int maxy, int rmax, const char
   snprintf(head, sizeof head, "#define LT_JIT_INDEX 1\n#define LT_JIT_BAND_T %s\n", BT);
   src += head;
   // A/B runs: LT_JIT_DEFINES="NAME=VALUE,NAME2=VALUE2" adds compile-time switches of the kernel
-  // headers (LT_RESOLVE_FULL, LT_WB, ...) to the generated source (and so to its cache key)
+  // headers (LT_WB, LT_DP_TRIPLE, LT_DP_NEIGHBOUR, LT_CERT_RULES, LT_PASSB_SLOTS, ...) to the
+  // generated source (and so to its cache key); a removed switch stops the compile (lt_fast.h)
   if (const char* e = getenv("LT_JIT_DEFINES")) {
     std::string s(e);
     size_t at = 0;
