@@ -392,6 +392,43 @@ typedef struct {
  * grown on demand). A failing strip's rows are unspecified; every other strip is decoded. */
 int lt_tiff_decode_strips_dev(lt_ctx* ctx, const lt_strips_job* jobs, int n_jobs, void* stream);
 
+/* ---- ingest: TIFF tiles and Deflate decoded on the device (an added export of ABI 8) -------------
+ * One TIFF image, strip- or tile-organised, whose compressed chunks (strips or tiles) are in
+ * device memory: the arguments of lt_tiff_decode_chunks (include/lt_io.h), every pointer a DEVICE
+ * pointer. lt_strips_job's fields with n_chunks for n_strips and chunk_h for rows_per_strip, plus
+ * chunk_w and tiled. */
+typedef struct {
+  const uint8_t* file;      /* DEVICE: the bytes that hold every chunk (the file, or a slice of it) */
+  int64_t file_size;
+  const uint64_t* offsets;  /* DEVICE [n_chunks], relative to `file`                                */
+  const uint64_t* counts;   /* DEVICE [n_chunks]                                                    */
+  int64_t n_chunks;         /* at least the image's: ceil(H / chunk_h) strips, or
+                               ceil(W / chunk_w) * ceil(H / chunk_h) tiles, per band when planar 2  */
+  int32_t compression;      /* 1, 5 or 8 (Deflate; the caller maps 32946 to 8)                      */
+  int32_t predictor;        /* 1 or 2                                                               */
+  int32_t bps;              /* bytes per sample: 1, 2, 4, 8                                         */
+  int32_t big_endian;
+  int64_t width, height;
+  int32_t bands, planar;    /* planar 1 (chunky: de-interleaved here) or 2                          */
+  int64_t chunk_w, chunk_h; /* tiles: the tile's size (tags 322, 323); strips: the image's width
+                               and the rows per strip                                               */
+  int32_t tiled;            /* 0 strips (the last one short), 1 tiles (all full, edges clipped)     */
+  void* out;                /* DEVICE [bands][height][width], native byte order                     */
+  int32_t* err;             /* DEVICE one word: zeroed by the call, then the LT_IO_ERR_* of some
+                               failing chunk (first writer wins, atomicCAS from 0), else 0          */
+} lt_chunks_job;
+/* lt_tiff_decode_chunks (lt_io.h) for n_jobs images whose compressed chunks are in device memory,
+ * asynchronous on `stream`; same results, same zero padding of short chunks, same ignored extra
+ * chunks. LT_ERR_ARG, before anything is launched, for a null pointer, a non-positive size, a
+ * compression, predictor or planar value outside the lists above, strips whose chunk_w is not the
+ * width, fewer chunks than the image has, and chunks of 1 MiB or more decoded. One lane per chunk
+ * (land_trendr_amd/csrc/lt_chunk.h over lt_lzw_core.h and lt_inflate_core.h, the sources
+ * liblt_io.so's lt_tiff_decode_chunks is compiled from), at most 32768 in flight; a wave's Huffman
+ * tables are in LDS, the context owns the LZW string tables (16 KB a lane, LZW images only) and
+ * the lanes' chunk buffers (tiles and chunky chunks; at most 1 GiB), grown on demand. A failing
+ * chunk's pixels are unspecified; every other chunk is decoded. */
+int lt_tiff_decode_chunks_dev(lt_ctx* ctx, const lt_chunks_job* jobs, int n_jobs, void* stream);
+
 /* ---- output: TIFF strips encoded on the device (an added export of ABI 8) -------------------------
  * One raster in device memory to its strips: the arguments of lt_tiff_encode_strips
  * (include/lt_io.h), every pointer a DEVICE pointer. */

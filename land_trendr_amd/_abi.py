@@ -161,6 +161,18 @@ class LtStripsJob(ctypes.Structure):
                 ('err', ctypes.c_void_p)]
 
 
+class LtChunksJob(ctypes.Structure):
+    """lt_chunks_job: one TIFF image (strips or tiles) whose chunks are in device memory."""
+    _fields_ = [('file', ctypes.c_void_p), ('file_size', ctypes.c_int64),
+                ('offsets', ctypes.c_void_p), ('counts', ctypes.c_void_p),
+                ('n_chunks', ctypes.c_int64), ('compression', ctypes.c_int32),
+                ('predictor', ctypes.c_int32), ('bps', ctypes.c_int32),
+                ('big_endian', ctypes.c_int32), ('width', ctypes.c_int64),
+                ('height', ctypes.c_int64), ('bands', ctypes.c_int32), ('planar', ctypes.c_int32),
+                ('chunk_w', ctypes.c_int64), ('chunk_h', ctypes.c_int64),
+                ('tiled', ctypes.c_int32), ('out', ctypes.c_void_p), ('err', ctypes.c_void_p)]
+
+
 class LtEncodeJob(ctypes.Structure):
     """lt_encode_job: one raster in device memory to its TIFF strips."""
     _fields_ = [('in_', ctypes.c_void_p), ('bands', ctypes.c_int32), ('bps', ctypes.c_int32),
@@ -230,7 +242,7 @@ EXPORTS = ['lt_abi_version', 'lt_ctx_create', 'lt_ctx_destroy', 'lt_last_error',
            'lt_index_linearize', 'lt_ctx_set_jit_mode', 'lt_jit_prepare', 'lt_ctx_jit_stats',
            'lt_jit_source', 'lt_analyze_tiles_ev', 'lt_tiff_decode_strips_dev',
            'lt_tiff_encode_strips_dev', 'lt_grid_sample_dev', 'lt_mask_codegen',
-           'lt_mask_compile', 'lt_mask_apply']
+           'lt_mask_compile', 'lt_mask_apply', 'lt_tiff_decode_chunks_dev']
 
 LT_JIT_SYNC, LT_JIT_ASYNC = 0, 1
 LT_JIT_SRC_SPEC, LT_JIT_SRC_SCENE, LT_JIT_SRC_FIELDS = 1, 2, 4
@@ -312,6 +324,7 @@ def load_lib(path=None):
                                   ctypes.c_int32, ctypes.c_char_p, ctypes.c_int64]
     lib.lt_jit_source.restype = ctypes.c_int
     lib.lt_tiff_decode_strips_dev.argtypes = [vp, ctypes.POINTER(LtStripsJob), ctypes.c_int, vp]
+    lib.lt_tiff_decode_chunks_dev.argtypes = [vp, ctypes.POINTER(LtChunksJob), ctypes.c_int, vp]
     lib.lt_tiff_encode_strips_dev.argtypes = [vp, ctypes.POINTER(LtEncodeJob), ctypes.c_int, vp]
     lib.lt_grid_sample_dev.argtypes = [vp, ctypes.POINTER(LtSampleJob), ctypes.c_int, vp]
     if lib.lt_abi_version() != LT_ABI_VERSION:

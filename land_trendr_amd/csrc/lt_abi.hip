@@ -308,6 +308,7 @@ struct lt_ctx {
   bool tl_split = false;
   lt::DecodeScratch dec;  // the strip decoder's scratch (lt_decode.hip)
   lt::EncodeScratch enc;  // the strip encoder's scratch (lt_encode.hip)
+  lt::ChunkScratch chk;   // the chunk decoder's scratch (lt_chunks.hip)
 };
 
 static int fail(lt_ctx* c, int code, const char* fmt, const char* detail = "") {
@@ -322,6 +323,7 @@ static int fail(lt_ctx* c, int code, const char* fmt, const char* detail = "") {
 namespace lt {  // the context as lt_decode.hip and lt_encode.hip see it (lt_launch.h)
 DecodeScratch& ctx_decode(lt_ctx* c) { return c->dec; }
 EncodeScratch& ctx_encode(lt_ctx* c) { return c->enc; }
+ChunkScratch& ctx_chunks(lt_ctx* c) { return c->chk; }
 int ctx_device(const lt_ctx* c) { return c->device; }
 int ctx_fail(lt_ctx* c, int code, const char* fmt, const char* detail) {
   return fail(c, code, fmt, detail);
@@ -433,6 +435,7 @@ int lt_ctx_destroy(lt_ctx* c) {
   if (c->d_xtab) (void)hipFree(c->d_xtab);
   lt::decode_release(c->dec);
   lt::encode_release(c->enc);
+  lt::chunks_release(c->chk);
   for (auto& kv : c->index_fns) {
     if (kv.second->mod) (void)hipModuleUnload(kv.second->mod);
     delete kv.second;

@@ -16,6 +16,8 @@
 #include <vector>
 
 #include "../../include/lt_io.h"
+#include "lt_chunk.h"
+#include "lt_inflate_core.h"
 #include "lt_lzw_core.h"
 #include "lt_sample.h"
 
@@ -429,6 +431,43 @@ int64_t lt_lzw_decode_core(const uint8_t* in, int64_t n_in, uint8_t* out, int64_
 int64_t lt_lzw_encode_core(const uint8_t* in, int64_t n_in, uint8_t* out, int64_t cap) {
   uint32_t table[lt_lzw::kEncSlots];
   return lt_lzw::encode(in, n_in, out, cap, lt_lzw::FlatTable{table});
+}
+
+// The zlib / Deflate decoder the device runs (lt_inflate_core.h, lt_chunks.hip), compiled for the
+// host: what the CPU tests and the sanitizer program drive.
+int64_t lt_inflate_core(const uint8_t* in, int64_t n_in, uint8_t* out, int64_t cap) {
+  uint16_t table[lt_inflate::kEntries];
+  return lt_inflate::decode(in, n_in, out, cap, lt_inflate::FlatTable{table});
+}
+
+// The chunk decoder the device runs (lt_chunk.h, lt_chunks.hip), compiled for the host: every
+// chunk over the pool; a failing chunk does not stop the others (the first error is returned).
+int64_t lt_tiff_decode_chunks(const uint8_t* file, int64_t file_size, const uint64_t* offsets,
+                              const uint64_t* counts, int64_t n_chunks, int compression,
+                              int predictor, int bps, int big_endian, int64_t width,
+                              int64_t height, int bands, int planar, int64_t chunk_w,
+                              int64_t chunk_h, int tiled, uint8_t* out, int threads) {
+  const lt_chunk::Image I =
+      lt_chunk::make_image(file, file_size, offsets, counts, compression, predictor, bps,
+                           big_endian, width, height, bands, planar, chunk_w, chunk_h, tiled, out);
+  if (lt_chunk::bad_image(I, n_chunks)) return LT_IO_ERR_ARG;
+  const int64_t tmp_bytes = lt_chunk::staged(I) ? lt_chunk::chunk_bytes(I) : 0;
+  std::atomic<int64_t> err(0);
+  pool_run(lt_chunk::image_chunks(I), threads, [&](int64_t k) -> int64_t {
+    static thread_local std::vector<uint8_t> tmp;
+    static thread_local std::vector<uint32_t> lzw;
+    uint16_t huff[lt_inflate::kEntries];
+    if ((int64_t)tmp.size() < tmp_bytes) tmp.resize((size_t)tmp_bytes);
+    if (compression == 5 && lzw.empty()) lzw.resize(4096);
+    const int rc = lt_chunk::decode_chunk(I, k, lt_lzw::FlatTable{lzw.data()},
+                                          lt_inflate::FlatTable{huff}, tmp.data());
+    if (rc < 0) {
+      int64_t z = 0;
+      err.compare_exchange_strong(z, rc);
+    }
+    return 0;
+  });
+  return err.load();
 }
 
 // The sampling core the device runs (lt_sample.h, lt_sample.hip), compiled for the host: the

@@ -64,9 +64,25 @@ struct EncodeScratch {
   int n_sets = 0;
 };
 void encode_release(EncodeScratch& s);
+// The chunk decoder's share of a context (lt_chunks.hip, lt_tiff_decode_chunks_dev): scratch grown
+// on demand, freed with the context (chunks_release), one set per stream like the strip decoder's.
+struct ChunkScratch {
+  struct Set {
+    uint32_t* d_tables = nullptr;  // LZW images: the lanes' string tables, as DecodeScratch's
+    int64_t table_lanes = 0;
+    uint8_t* d_chunks = nullptr;   // tiles and chunky chunks: one decoded chunk per lane
+    int64_t chunks_bytes = 0;
+  };
+  static constexpr int kMaxSets = 16;
+  hipStream_t stream[kMaxSets] = {};
+  Set set[kMaxSets];
+  int n_sets = 0;
+};
+void chunks_release(ChunkScratch& s);
 // What lt_decode.hip and lt_encode.hip need of a context (defined in lt_abi.hip beside lt_ctx).
 DecodeScratch& ctx_decode(lt_ctx* c);
 EncodeScratch& ctx_encode(lt_ctx* c);
+ChunkScratch& ctx_chunks(lt_ctx* c);
 int ctx_device(const lt_ctx* c);
 int ctx_fail(lt_ctx* c, int code, const char* fmt, const char* detail);
 

@@ -353,9 +353,35 @@ class Engine:
         Returns (the list of [bands, height, width] tensors, native byte order; the int32 error
         words, one per job: 0, or the LT_IO_ERR_* of a failing strip once the stream has run).
         Asynchronous on `stream`; the caller keeps the input tensors alive until it has run."""
+        def fill(a, j, n_strips):
+            a.n_strips, a.compression = n_strips, int(j['compression'])
+            a.rows_per_strip = int(j['rows_per_strip'])
+        return self._decode_jobs('decode_strips', _abi.LtStripsJob, fill,
+                                 'lt_tiff_decode_strips_dev', jobs, stream)
+
+    # --- ingest: TIFF tiles and Deflate decoded on the device (lt_tiff_decode_chunks_dev) ---
+    def decode_chunks(self, jobs, stream=None):
+        """decode_strips for strips or tiles, uncompressed, LZW or Deflate (the HIP chunk decoder,
+        lt_chunks.hip). A job is decode_strips's dict with, instead of rows_per_strip:
+          compression  1, 5, 8 or 32946 (Deflate);
+          chunk_w, chunk_h  the tile size, or the image's width and the rows per strip;
+          tiled        whether the offsets are tiles (all full size) or strips.
+        Same return, same error words (one per job), same asynchrony and lifetime rules."""
+        def fill(a, j, n_chunks):
+            comp = int(j['compression'])
+            a.n_chunks, a.compression = n_chunks, 8 if comp == 32946 else comp
+            a.chunk_w, a.chunk_h = int(j['chunk_w']), int(j['chunk_h'])
+            a.tiled = 1 if j['tiled'] else 0
+        return self._decode_jobs('decode_chunks', _abi.LtChunksJob, fill,
+                                 'lt_tiff_decode_chunks_dev', jobs, stream)
+
+    def _decode_jobs(self, what, struct, fill, entry, jobs, stream):
+        """decode_strips's and decode_chunks's common part: the outputs and error words made on
+        the stream, the checks of out / file / offsets / counts, the fields the two job structs
+        share, fill(a, j) for the others, then the library call `entry` under the decode lock."""
         import numpy as np
         n = len(jobs)
-        arr = (_abi.LtStripsJob * max(n, 1))()
+        arr = (struct * max(n, 1))()
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
         with torch.cuda.stream(st):  # (tensors made here belong to the stream that fills them)
             err = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)  # zeroed by the call
@@ -372,35 +398,35 @@ class Engine:
             out = j.get('out') if j.get('out') is not None else made[k]
             if (tuple(out.shape) != shape or out.dtype != tdt or out.device != self.device or
                     not out.is_contiguous()):
-                raise LtError('decode_strips: out must be a contiguous %s %s tensor on %s'
-                              % (tdt, shape, self.device))
+                raise LtError('%s: out must be a contiguous %s %s tensor on %s'
+                              % (what, tdt, shape, self.device))
             f, offs, cnts = j['file'], j['offsets'], j['counts']
             if (f.dtype != torch.uint8 or f.dim() != 1 or not f.is_contiguous() or
                     f.device != self.device):
-                raise LtError('decode_strips: file must be a contiguous uint8 tensor on %s'
-                              % self.device)
+                raise LtError('%s: file must be a contiguous uint8 tensor on %s'
+                              % (what, self.device))
             for t in (offs, cnts):
                 if (t.dtype not in (torch.int64, torch.uint64) or t.dim() != 1 or
                         not t.is_contiguous() or t.device != self.device or
                         t.shape != offs.shape):
-                    raise LtError('decode_strips: offsets / counts must be contiguous 64-bit '
-                                  '[n_strips] tensors on %s' % self.device)
+                    raise LtError('%s: offsets / counts must be contiguous 64-bit [n] tensors '
+                                  'on %s' % (what, self.device))
             a = arr[k]
             a.file, a.file_size = f.data_ptr(), f.numel()
-            a.offsets, a.counts, a.n_strips = offs.data_ptr(), cnts.data_ptr(), offs.numel()
-            a.compression, a.predictor = int(j['compression']), int(j['predictor'])
+            a.offsets, a.counts = offs.data_ptr(), cnts.data_ptr()
+            a.predictor = int(j['predictor'])
             a.bps = dt.itemsize
             a.big_endian = 1 if (dt.byteorder == '>' or
                                  (dt.byteorder == '=' and np.little_endian is False)) else 0
             a.width, a.height, a.bands = shape[2], shape[1], shape[0]
-            a.planar, a.rows_per_strip = int(j['planar']), int(j['rows_per_strip'])
+            a.planar = int(j['planar'])
             a.out = out.data_ptr()
             a.err = err.data_ptr() + 4 * k
+            fill(a, j, offs.numel())
             outs.append(out)
         with self._decode_lock:  # one context: one caller at a time (ingest decodes on threads)
-            self._check(self.lib.lt_tiff_decode_strips_dev(self.ctx, arr, n,
-                                                           ctypes.c_void_p(st.cuda_stream)),
-                        'lt_tiff_decode_strips_dev')
+            self._check(getattr(self.lib, entry)(self.ctx, arr, n,
+                                                 ctypes.c_void_p(st.cuda_stream)), entry)
         return outs, err[:n]
 
     # --- output: TIFF strips encoded on the device (lt_tiff_encode_strips_dev, lt_encode.hip) ---

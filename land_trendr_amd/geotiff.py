@@ -231,19 +231,33 @@ class GeoTiff:
         raises TiffError and nothing is decoded. Returns (out, error word)."""
         if not self.device_eligible():
             raise TiffError('not eligible for the device decoder (GeoTiff.device_eligible)')
-        import torch
-        from .engine import LtError
         t = self.tags
         H, B = self.height, self.bands
         rps = min(int(t.get(278, (H,))[0]), H)
         per_band = -(-H // rps)
         need = per_band if self.planar == 1 else per_band * B
-        offs = np.asarray(t[273], np.int64)
-        cnts = np.asarray(t[279], np.int64)
+
+        def decode(file, offsets, counts, st):
+            return engine.decode_strips([dict(
+                file=file, offsets=offsets, counts=counts,
+                compression=self.compression, predictor=self.predictor, dtype=self.dtype,
+                width=self.width, height=H, bands=B, planar=self.planar, rows_per_strip=rps,
+                out=out)], stream=st)
+        return self._staged_decode(engine, t[273], t[279], need, decode, stream, check, staging,
+                                   'strips')
+
+    def _staged_decode(self, engine, offsets, counts, need, decode, stream, check, staging, what):
+        """read_device's and read_device_chunks's common part: the byte range that spans the first
+        `need` chunks into `staging`, the offsets and counts behind it, one copy to the device,
+        the event self.staged, then decode(file, offsets, counts, stream) -> (outs, err)."""
+        import torch
+        from .engine import LtError
+        offs = np.asarray(offsets, np.int64)
+        cnts = np.asarray(counts, np.int64)
         if len(offs) < need or len(cnts) != len(offs):
-            raise TiffError('TIFF strips: fewer strips than the image has')
+            raise TiffError('TIFF %s: fewer %s than the image has' % (what, what))
         size = len(self._d)
-        # the bytes sent: from the first to the last strip that lies inside the file (a strip
+        # the bytes sent: from the first to the last chunk that lies inside the file (a chunk
         # that does not keeps its offset, now outside the slice: the decoder reports it)
         inside = (offs[:need] >= 0) & (cnts[:need] >= 0) & (offs[:need] + cnts[:need] <= size)
         lo = int(offs[:need][inside].min()) if inside.any() else 0
@@ -268,19 +282,77 @@ class GeoTiff:
                 self.staged = torch.cuda.Event()
                 self.staged.record(st)
                 dt = d[n8:].view(torch.int64)
-                outs, err = engine.decode_strips([dict(
-                    file=d[:n] if n else d[:0], offsets=dt[:len(offs)], counts=dt[len(offs):],
-                    compression=self.compression, predictor=self.predictor, dtype=self.dtype,
-                    width=self.width, height=H, bands=B, planar=self.planar, rows_per_strip=rps,
-                    out=out)], stream=st)
+                outs, err = decode(d[:n] if n else d[:0], dt[:len(offs)], dt[len(offs):], st)
         except LtError as e:
             raise TiffError(str(e))
         if check:
             st.synchronize()
             rc = int(err.item())
             if rc != 0:
-                raise TiffError('TIFF strips: corrupt or unsupported data (%d)' % rc)
+                raise TiffError('TIFF %s: corrupt or unsupported data (%d)' % (what, rc))
         return outs[0], err
+
+    def chunk_layout(self):
+        """(offsets tag, counts tag, chunk_w, chunk_h, tiled, chunks the image has) of the file's
+        strips or tiles, or None when it has neither (or a non-positive size)."""
+        t = self.tags
+        W, H, B = self.width, self.height, self.bands
+        if W <= 0 or H <= 0 or B <= 0:
+            return None
+        if 273 in t and 279 in t:
+            rps = min(int(t.get(278, (H,))[0]), H)
+            if rps <= 0:
+                return None
+            per = -(-H // rps)
+            return 273, 279, W, rps, False, per if self.planar == 1 else per * B
+        if 324 in t and 325 in t and 322 in t and 323 in t:
+            tw, th = int(t[322][0]), int(t[323][0])
+            if tw <= 0 or th <= 0:
+                return None
+            per = (-(-W // tw)) * (-(-H // th))
+            return 324, 325, tw, th, True, per if self.planar == 1 else per * B
+        return None
+
+    def device_chunks_eligible(self):
+        """Whether read_device_chunks takes this file: strips or tiles, uncompressed, LZW or
+        Deflate (8, 32946), predictor 1 (or 2 with integer samples), 8/16/32/64-bit samples,
+        chunky or planar, chunks that decode to less than 1 MiB. Every device_eligible() file is
+        among them; predictor 3, PackBits and larger chunks are the host's."""
+        if self.compression not in (1, 5, 8, 32946):
+            return False
+        if not (self.predictor == 1 or (self.predictor == 2 and self.dtype.kind in 'iu')):
+            return False
+        if self.bits not in (8, 16, 32, 64) or self.planar not in (1, 2):
+            return False
+        lay = self.chunk_layout()
+        if lay is None:
+            return False
+        spp = self.bands if self.planar == 1 else 1
+        return lay[2] * lay[3] * spp * self.dtype.itemsize < (1 << 20)
+
+    def read_device_chunks(self, engine, out=None, stream=None, check=True, staging=None):
+        """read_device for every device_chunks_eligible() file (tiles, Deflate; strips and LZW as
+        well), decoded by engine.decode_chunks: the same staging, `staged` event, error word and
+        return. A file that is not eligible raises TiffError before the engine is touched."""
+        if not self.device_chunks_eligible():
+            raise TiffError('not eligible for the device chunk decoder '
+                            '(GeoTiff.device_chunks_eligible)')
+        otag, ctag, cw, ch, tiled, need = self.chunk_layout()
+
+        def decode(file, offsets, counts, st):
+            return engine.decode_chunks([dict(
+                file=file, offsets=offsets, counts=counts,
+                compression=self.compression, predictor=self.predictor, dtype=self.dtype,
+                width=self.width, height=self.height, bands=self.bands, planar=self.planar,
+                chunk_w=cw, chunk_h=ch, tiled=tiled, out=out)], stream=st)
+        return self._staged_decode(engine, self.tags[otag], self.tags[ctag], need, decode, stream,
+                                   check, staging, 'tiles' if tiled else 'strips')
+
+    def staging_bytes(self):
+        """An upper bound of the pinned bytes read_device / read_device_chunks stage."""
+        lay = self.chunk_layout()
+        n = len(self.tags[lay[0]]) if lay else 0
+        return len(self._d) + 16 * n + 16
 
 
 def read_bands(path):

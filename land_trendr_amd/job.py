@@ -95,7 +95,8 @@ class _LazyBands(dict):
 class LocalJob:
     def __init__(self, root, job, device=None, tile_pixels=1 << 22, trendline=True,
                  raster_mode='reference', pre_threshold_mode='reference', on_error='raise',
-                 work_dir=None, engine=None, decode=None, encode=None, sample=None):
+                 work_dir=None, engine=None, decode=None, encode=None, sample=None,
+                 device_formats=None):
         """engine: the analysis engine (default: engine.get_engine of `device`, the HIP library);
         tests pass a CPU double (tests/engine_double.py) to run the multi-rank path over gloo.
         decode: 'host' (default; LT_JOB_DECODE overrides the default) — every raster's strips are
@@ -116,7 +117,16 @@ class LocalJob:
         (Engine.sample_grid) into its plane and validity row of the device stack, whatever its
         extent and band count, and so is its mask (strip-organised, integer samples); the others
         as with 'host'; sample_stats counts the rasters sampled on the device and the masks by
-        path."""
+        path.
+        device_formats: 'strips' (default; LT_JOB_DEVICE_FORMATS overrides the default) — the
+        device decoder is offered the strip-organised uncompressed and LZW files
+        (GeoTiff.device_eligible), as before; 'all' (needs decode='device') — every file the HIP
+        chunk decoder takes (GeoTiff.device_chunks_eligible: tiles and Deflate as well, through
+        GeoTiff.read_device_chunks), in the in-place decode and, with sample='device', for the
+        sampled rasters and their masks; decode_stats and sample_stats count as before. As
+        measured (DESIGN.md § Tiles and Deflate decoded on the GPU) 'all' pays for Deflate strip
+        files only: tiled files decode several times slower on the device than on the host, and
+        'all' sends them there all the same."""
         if on_error not in ('raise', 'skip'):
             raise ValueError('on_error must be "raise" or "skip"')
         decode = decode or os.environ.get('LT_JOB_DECODE') or 'host'
@@ -135,6 +145,12 @@ class LocalJob:
         if sample == 'device' and decode != 'device':
             raise ValueError('sample="device" needs decode="device"')
         self.sample = sample
+        device_formats = device_formats or os.environ.get('LT_JOB_DEVICE_FORMATS') or 'strips'
+        if device_formats not in ('strips', 'all'):
+            raise ValueError('device_formats must be "strips" or "all"')
+        if device_formats == 'all' and decode != 'device':
+            raise ValueError('device_formats="all" needs decode="device"')
+        self.device_formats = device_formats
         # rasters sampled on the device (Engine.sample_grid), cloud masks by where they were applied
         self.sample_stats = {'rasters': 0, 'masks_device': 0, 'masks_host': 0}
         # settings.json mask_eqn: {'eqn', 'observations' (valid observation-pixels of this rank's
@@ -364,13 +380,21 @@ class LocalJob:
                 host[k] = dev[k].cpu().numpy()
         return fill if sampled else None
 
+    def device_takes(self, ds):
+        """Whether a decode='device' job offers this open GeoTiff to the device decoder: by
+        device_formats, GeoTiff.device_eligible ('strips') or device_chunks_eligible ('all')."""
+        if self.device_formats == 'all':
+            return ds.device_chunks_eligible()
+        return ds.device_eligible()
+
     def _device_decoder(self, up, K, nb, Q, eqn_bands=None):
         """ingest_stack's device_decode of a decode='device' job (None: host decode for the whole
         job — no GPU uploader, or a stack above the 64 GB rule analyze() applies for the whole-stack
         upload). Makes the [K, nb, Q] device stack up front in the first raster's sample type;
         each accepted raster is staged in a pinned buffer of the calling worker thread and decoded
-        on one of a few streams (GeoTiff.read_device, check=False: check() reads every error
-        word once parse has synchronised)."""
+        on one of a few streams (GeoTiff.read_device, or read_device_chunks with
+        device_formats='all'; check=False: check() reads every error word once parse has
+        synchronised)."""
         import threading
         import torch
         if up is None:
@@ -400,6 +424,15 @@ class LocalJob:
         sel = [b - 1 for b in (eqn_bands or [])]
         axes = getattr(self, '_grid_axes', None) if self.raster_grid is not None else None
         offsets = {}
+        what = 'strips or tiles' if self.device_formats == 'all' else 'strips'
+        # device_formats: which files are offered to the device, and the reader that takes them
+        eligible = self.device_takes
+        if self.device_formats == 'all':
+            def read_device(ds, **kw):
+                return ds.read_device_chunks(eng, **kw)
+        else:
+            def read_device(ds, **kw):
+                return ds.read_device(eng, **kw)
 
         class Dec:
             def __init__(self):
@@ -417,7 +450,7 @@ class LocalJob:
                         tl.stream = streams[self.threads % len(streams)]
                         self.threads += 1
                     tl.staging, tl.staged, tl.scratch = None, None, None
-                need = len(ds._d) + 16 * len(ds.tags[273]) + 16
+                need = ds.staging_bytes()  # (the strip or the tile tags' entries)
                 t0 = time.perf_counter()
                 if tl.staged is not None:  # the previous raster's bytes have left the buffer
                     tl.staged.synchronize()
@@ -433,8 +466,8 @@ class LocalJob:
                             tl.scratch = torch.empty(n, dtype=torch.uint8, device=up.device)
                     tdt = torch.from_numpy(np.empty(0, ds.dtype.newbyteorder('='))).dtype
                     out = tl.scratch[:n].view(tdt).view(ds.bands, ds.height, ds.width)
-                _, err = ds.read_device(eng, out=out, stream=tl.stream, check=False,
-                                        staging=tl.staging)
+                _, err = read_device(ds, out=out, stream=tl.stream, check=False,
+                                     staging=tl.staging)
                 t3 = time.perf_counter()
                 tl.staged = ds.staged
                 return out, err, (t1 - t0, t2 - t1, t3 - t2)
@@ -444,7 +477,7 @@ class LocalJob:
                     self.times[key] += dt
 
             def __call__(self, k, ds):
-                if (not ds.device_eligible() or ds.bands != nb or
+                if (not eligible(ds) or ds.bands != nb or
                         ds.dtype.newbyteorder('=') != dtype or ds.width * ds.height != Q):
                     return False
                 _, err, dts = self._read(ds, up.bands[k].view(ds.bands, ds.height, ds.width))
@@ -470,11 +503,11 @@ class LocalJob:
                 """ingest_stack's device_sample: raster k and its mask decoded into this worker's
                 scratch raster and sampled at the stack's pixel ranges (Engine.sample_grid), all on
                 the worker's stream."""
-                if (axes is None or not sel or not ds.device_eligible() or
+                if (axes is None or not sel or not eligible(ds) or
                         ds.dtype.newbyteorder('=') != dtype or ds.bands < max(sel) + 1 or
                         max(ds.height, ds.width) >= 1 << 31):
                     return False
-                if mds is not None and not (mds.device_eligible() and mds.dtype.kind in 'iu' and
+                if mds is not None and not (eligible(mds) and mds.dtype.kind in 'iu' and
                                             max(mds.height, mds.width) < 1 << 31):
                     return False
                 for g, mode, name in ((ds, _abi.LT_SAMPLE_BANDS, rast_fns[k]),
@@ -502,8 +535,8 @@ class LocalJob:
                 for _, name, err in sorted(self.errs, key=lambda e: e[:2]):
                     rc = int(err.item())
                     if rc != 0:
-                        raise TiffError('%s: TIFF strips: corrupt or unsupported data (%d)'
-                                        % (name, rc))
+                        raise TiffError('%s: TIFF %s: corrupt or unsupported data (%d)'
+                                        % (name, what, rc))
         return Dec()
 
     def _stack_uploader(self, K, nb, Q):

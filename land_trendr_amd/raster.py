@@ -142,14 +142,17 @@ _GEO_TAGS = (33550, 33922, 34264, 34735, 34736, 34737)  # scale, tiepoint, trans
 
 
 def write_geotiff(path, array, template=None, nodata=NODATA, geotransform=None, compress='lzw',
-                  predictor=1, rows_per_strip=None):
+                  predictor=1, rows_per_strip=None, tile=None):
     """Little-endian GeoTIFF of a 2-D array, or of a 3-D [bands, rows, cols] array (planar
     configuration 2: each band's strips in turn, what GeoTiff.read returns as [bands, rows,
     cols]); georeferencing tags copied verbatim from `template` (a GeoTiff or a path), or written
     from a north-up `geotransform` (ModelPixelScale + ModelTiepoint), GDAL_NODATA set to `nodata`.
     compress: 'lzw' (array2raster's COMPRESS=LZW, utils.py:386; the native codec of
     tiffcodec.py), 'deflate' or None; predictor 2 (horizontal differencing) for integer samples.
-    Strips of about 8 KB of raw samples, as GDAL's GTiff driver lays them out."""
+    Strips of about 8 KB of raw samples, as GDAL's GTiff driver lays them out.
+    tile=(th, tw), multiples of 16: a tiled file instead (GDAL's TILED=YES; tags 322-325), every
+    tile full size, the edge tiles padded with zeros, each band's tiles in turn, encoded on the
+    host's threads."""
     from . import tiffcodec
     a = np.ascontiguousarray(array)
     if a.ndim not in (2, 3) or a.dtype.kind not in _SAMPLE_FORMAT:
@@ -162,6 +165,28 @@ def write_geotiff(path, array, template=None, nodata=NODATA, geotransform=None, 
         a = a[None]
     nb, rows, cols = a.shape
     tmpl = GeoTiff(template) if isinstance(template, str) else template
+    if tile is not None:
+        th, tw = (int(v) for v in tile)
+        if th <= 0 or tw <= 0 or th % 16 or tw % 16:
+            raise ValueError('write_geotiff: tile sizes are positive multiples of 16')
+        from concurrent.futures import ThreadPoolExecutor
+        from .ingest import host_threads
+
+        def one(pos):  # (zlib and the LZW encoder run outside the interpreter lock)
+            b, y0, x0 = pos
+            blk = np.zeros((th, tw), a.dtype)
+            part = a[b, y0:y0 + th, x0:x0 + tw]
+            blk[:part.shape[0], :part.shape[1]] = part
+            if predictor == 2:
+                blk = tiffcodec.apply_predictor2(blk, tw, 1)
+            return tiffcodec.encode(comp, np.ascontiguousarray(blk).tobytes())
+        where = [(b, y0, x0) for b in range(nb) for y0 in range(0, rows, th)
+                 for x0 in range(0, cols, tw)]
+        with ThreadPoolExecutor(max(1, host_threads())) as pool:
+            tiles = list(pool.map(one, where))
+        return write_tiff_strips(path, b''.join(tiles), [len(t) for t in tiles], (nb, rows, cols),
+                                 a.dtype, comp, predictor, None, tmpl, geotransform, nodata,
+                                 tile=(th, tw))
     rps = _strip_rows(rows, cols, a.dtype.itemsize, rows_per_strip)
     if tiffcodec.native_strips(comp, predictor, a.dtype.itemsize * 8):
         # every strip on the host's threads (liblt_io.so lt_tiff_encode_strips)
@@ -181,12 +206,13 @@ def write_geotiff(path, array, template=None, nodata=NODATA, geotransform=None, 
 
 
 def write_tiff_strips(path, data, sizes, shape, dtype, comp, predictor, rps, tmpl=None,
-                      geotransform=None, nodata=NODATA):
+                      geotransform=None, nodata=NODATA, tile=None):
     """The file write_geotiff lays out, from strips that are already encoded: `data` holds them
     back to back (band-major, then row order; a bytes-like object or a uint8 array of exactly
     sum(sizes) bytes), `sizes` their byte counts; shape (bands, rows, cols), dtype the sample
     type, comp / predictor the TIFF tag values the strips were encoded with, rps the rows per
-    strip, tmpl a GeoTiff or None."""
+    strip, tmpl a GeoTiff or None. tile=(th, tw): `data` holds tiles (band-major, then row-major
+    over the tile grid) and the tile tags are written instead of the strip tags."""
     nb, rows, cols = shape
     dtype = np.dtype(dtype)
     sizes = [int(v) for v in sizes]
@@ -211,10 +237,16 @@ def write_tiff_strips(path, data, sizes, shape, dtype, comp, predictor, rps, tmp
         add(258, 3, [dtype.itemsize * 8] * nb, 'H')
         add(259, 3, [comp], 'H')
         add(262, 3, [1], 'H')
-        add(273, 4, offs, 'I')
         add(277, 3, [nb], 'H')
-        add(278, 4, [rps], 'I')
-        add(279, 4, sizes, 'I')
+        if tile is None:
+            add(273, 4, offs, 'I')
+            add(278, 4, [rps], 'I')
+            add(279, 4, sizes, 'I')
+        else:
+            add(322, 4, [tile[1]], 'I')
+            add(323, 4, [tile[0]], 'I')
+            add(324, 4, offs, 'I')
+            add(325, 4, sizes, 'I')
         add(284, 3, [2 if nb > 1 else 1], 'H')
         if predictor == 2:
             add(317, 3, [2], 'H')
@@ -277,12 +309,15 @@ def _strip_rows(rows, cols, itemsize, rows_per_strip=None):
     return rows_per_strip or max(1, min(rows, 8192 // max(1, cols * itemsize)))
 
 
-def device_encodable(dtype, shape, compress='lzw', predictor=1, rows_per_strip=None):
+def device_encodable(dtype, shape, compress='lzw', predictor=1, rows_per_strip=None, tile=None):
     """Whether write_geotiff_device encodes this raster on the device: LZW or no compression,
-    predictor 1 or 2, 1, 2, 4 or 8 byte samples, strips of less than 1 MiB of raw bytes. Anything
+    predictor 1 or 2, 1, 2, 4 or 8 byte samples, strips (never tiles: tile is None) of less than
+    1 MiB of raw bytes. Anything
     else is write_geotiff's, which writes Deflate and large strips on the host and raises
     ValueError for what it does not write either (float samples with predictor 2)."""
     dtype = np.dtype(dtype)
+    if tile is not None:
+        return False
     if compress not in (None, 'none', 'lzw') or dtype.kind not in _SAMPLE_FORMAT:
         return False
     if predictor not in (1, 2) or (predictor == 2 and dtype.kind == 'f'):

@@ -2,7 +2,8 @@
 ds2array decodes any compression, utils.py:272-282; array2raster writes COMPRESS=LZW, :386).
 
   * LZW (Compression 5): native, land_trendr_amd/liblt_io.so (include/lt_io.h);
-  * Deflate (Compression 8 and the old 32946): zlib;
+  * Deflate (Compression 8 and the old 32946): zlib (inflate_core / decode_chunks: the host
+    builds of the decoders the device runs, lt_inflate_core.h and lt_chunk.h, for the tests);
   * PackBits (Compression 32773): restated here (run-length, byte oriented);
   * Predictor 2 (horizontal differencing, integer samples) undone / applied per row;
     Predictor 3 (floating point) is decoded too (byte planes, then differencing).
@@ -24,10 +25,13 @@ def _lib():
             raise RuntimeError('%s not built: run __graft_entry__.build()' % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
         for f in (L.lt_lzw_decode, L.lt_lzw_encode, L.lt_lzw_decode_core,
-                  L.lt_lzw_encode_core):
+                  L.lt_lzw_encode_core, L.lt_inflate_core):
             f.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64]
             f.restype = ctypes.c_int64
         i64, vp, ci = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
+        L.lt_tiff_decode_chunks.argtypes = [vp, i64, vp, vp, i64, ci, ci, ci, ci, i64, i64, ci, ci,
+                                            i64, i64, ci, vp, ci]
+        L.lt_tiff_decode_chunks.restype = i64
         L.lt_tiff_decode_strips.argtypes = [vp, i64, vp, vp, i64, ci, ci, ci, ci, i64, i64, ci, ci,
                                             i64, vp, ci]
         L.lt_tiff_decode_strips.restype = i64
@@ -57,6 +61,17 @@ def lzw_decode_core(data, size):
     n = _lib().lt_lzw_decode_core(bytes(data), len(data), out.ctypes.data, size)
     if n < 0:
         raise ValueError('LZW: corrupt strip (%d)' % n)
+    return out
+
+
+def inflate_core(data, size):
+    """One zlib stream -> `size` raw bytes by the Deflate core the device runs (lt_inflate_core.h,
+    host build): decode(8, data, size)'s bytes, a stream that ends early zero-padded; ValueError
+    for a stream zlib rejects before `size` bytes are out."""
+    out = np.zeros(size, np.uint8)
+    n = _lib().lt_inflate_core(bytes(data), len(data), out.ctypes.data, size)
+    if n < 0:
+        raise ValueError('Deflate: corrupt stream (%d)' % n)
     return out
 
 
@@ -186,6 +201,36 @@ def decode_strips(buf, offsets, counts, compression, predictor, dtype, big_endia
     if rc < 0:
         raise ValueError('TIFF strips: corrupt or unsupported data (%d)' % rc)
     return out
+
+
+def decode_chunks(buf, offsets, counts, compression, predictor, dtype, big_endian, width, height,
+                  bands, planar, chunk_w, chunk_h, tiled, threads=1, out=None, check=True):
+    """Every strip or tile of an image by the chunk decoder the device runs (lt_chunk.h, host
+    build: liblt_io.so lt_tiff_decode_chunks) -> ([bands, height, width] in native byte order,
+    the return code: 0 or the LT_IO_ERR_* of a failing chunk, every other chunk decoded).
+    check=True raises ValueError for a non-zero code; a rejected argument always raises."""
+    want = np.dtype(dtype).newbyteorder('=')
+    if out is None:
+        out = np.zeros((bands, height, width), want)
+    elif (out.shape != (bands, height, width) or out.dtype != want or
+          not out.flags.c_contiguous or not out.flags.writeable):
+        raise ValueError('decode_chunks: out must be a writable C-contiguous %s array of shape %s'
+                         % (want, (bands, height, width)))
+    offs = np.ascontiguousarray(offsets, np.uint64)
+    cnts = np.ascontiguousarray(counts, np.uint64)
+    if len(offs) != len(cnts):
+        raise ValueError('decode_chunks: offsets and counts differ in length')
+    src = np.frombuffer(buf, np.uint8)
+    rc = _lib().lt_tiff_decode_chunks(src.ctypes.data, src.size, offs.ctypes.data, cnts.ctypes.data,
+                                      len(offs), 8 if compression == 32946 else compression,
+                                      predictor, out.itemsize, 1 if big_endian else 0, width,
+                                      height, bands, planar, chunk_w, chunk_h, 1 if tiled else 0,
+                                      out.ctypes.data, max(1, int(threads)))
+    if rc == -1:
+        raise ValueError('decode_chunks: bad argument or unsupported layout')
+    if rc < 0 and check:
+        raise ValueError('TIFF chunks: corrupt or unsupported data (%d)' % rc)
+    return out, int(rc)
 
 
 def grid_sample(src, xoff, yoff, p0, n, sel, out, out_stride, valid, mode, threads=1):

@@ -43,7 +43,7 @@ SETTINGS = {'index_eqn': 'B1 - B2', 'line_cost': 10, 'target_date': '2014-07-01'
 
 
 def make_stack(root, job, rows, cols, years, seed, mask_prob, shift=0, mask_eqn=None,
-               qa_band=False):
+               qa_band=False, compress='lzw', tiff_tile=None):
     """The job directory: one two-band int16 LZW GeoTIFF per acquisition date (raster order:
     pixel p of the scene at row p // cols, column p % cols) and, with mask_prob > 0, a cloudmask
     raster per date. shift = N > 0: every N-th raster is written with an extent of its own — its
@@ -51,7 +51,8 @@ def make_stack(root, job, rows, cols, years, seed, mask_prob, shift=0, mask_eqn=
     (alternating), zeros outside the scene — and with two spare bands behind the two the index
     reads, as a LEDAPS stack's dates differ. mask_eqn / qa_band: every raster gets a third band
     (0 where the scene's mask is, 1 elsewhere); with mask_eqn the key goes into settings.json and
-    no cloudmask raster is written. Returns (seconds, bytes written)."""
+    no cloudmask raster is written. compress / tiff_tile: write_geotiff's compress and tile of
+    the rasters and masks. Returns (seconds, bytes written)."""
     import torch
     from land_trendr_amd.raster import write_geotiff
     from land_trendr_amd.synth import make_scene
@@ -85,12 +86,13 @@ def make_stack(root, job, rows, cols, years, seed, mask_prob, shift=0, mask_eqn=
             big[nb:] = 7
             img = big
             gt = (GT[0] + sx * GT[1], GT[1], 0.0, GT[3] + sy * GT[5], 0.0, GT[5])
-        write_geotiff(fn, img, geotransform=gt, nodata=None)
+        write_geotiff(fn, img, geotransform=gt, nodata=None, compress=compress, tile=tiff_tile)
         nbytes += os.path.getsize(fn)
         if sc.valid is not None and not mask_eqn:
             m = sc.valid[k].reshape(rows, cols).cpu().numpy()
             mf = os.path.join(rdir, stem + '_cloudmask.tif')
-            write_geotiff(mf, m, geotransform=GT, nodata=None)
+            write_geotiff(mf, m, geotransform=GT, nodata=None, compress=compress,
+                          tile=tiff_tile)
             nbytes += os.path.getsize(mf)
         if k % 5 == 4:
             print('  %d rasters written (%.0f s)' % (k + 1, time.time() - t0), file=sys.stderr,
@@ -209,20 +211,48 @@ def main():
     ap.add_argument('--encode', default='host', choices=('host', 'device'),
                     help="where the output rasters' strips are encoded (LocalJob encode=): "
                          'liblt_io.so on the host threads, or the HIP strip encoder on the GPU')
+    ap.add_argument('--compress', default='lzw', choices=('lzw', 'deflate'),
+                    help='compression of the input rasters and masks')
+    ap.add_argument('--tiff-tile', type=int, default=0,
+                    help='N > 0: the input rasters and masks are N x N tiled GeoTIFFs (a multiple '
+                         'of 16), not strips (--tile is the job\'s tile size in pixels)')
+    ap.add_argument('--device-formats', default='strips', choices=('strips', 'all'),
+                    help="what --decode device offers the GPU (LocalJob device_formats=): 'strips' "
+                         "uncompressed / LZW strip files, 'all' tiles and Deflate as well")
+    ap.add_argument('--reuse', action='store_true',
+                    help='use the stack an earlier --keep run left in --work (written with the '
+                         'same size and format options) instead of writing it again: runs that '
+                         'alternate over one stack')
     a = ap.parse_args()
     import torch
     from land_trendr_amd.ingest import host_threads
     from land_trendr_amd.job import LocalJob
-    shutil.rmtree(a.work, ignore_errors=True)
-    os.makedirs(a.work)
+    rdir = os.path.join(a.work, 'bench', 'input', 'rasters')
+    reuse = a.reuse and os.path.isdir(rdir)
+    if reuse:  # everything but the input goes
+        for d in (a.work, os.path.join(a.work, 'bench')):
+            for name in os.listdir(d):
+                if name not in ('bench', 'input'):
+                    q = os.path.join(d, name)
+                    shutil.rmtree(q) if os.path.isdir(q) else os.remove(q)
+    else:
+        shutil.rmtree(a.work, ignore_errors=True)
+        os.makedirs(a.work)
     try:
-        gen_s, in_bytes = make_stack(a.work, 'bench', a.rows, a.cols, a.years, a.seed, a.mask,
-                                        a.shift, a.mask_eqn, a.qa_cloudmask)
+        if reuse:
+            gen_s = 0.0
+            in_bytes = sum(os.path.getsize(os.path.join(rdir, f)) for f in os.listdir(rdir))
+        else:
+            gen_s, in_bytes = make_stack(a.work, 'bench', a.rows, a.cols, a.years, a.seed, a.mask,
+                                            a.shift, a.mask_eqn, a.qa_cloudmask, a.compress,
+                                            (a.tiff_tile, a.tiff_tile) if a.tiff_tile else None)
         print('stack written: %.1f s, %.2f GB' % (gen_s, in_bytes / 1e9), file=sys.stderr,
               flush=True)
         P = a.rows * a.cols
         j = LocalJob(a.work, 'bench', device=0, tile_pixels=a.tile, trendline=a.trendline,
-                     on_error='skip', decode=a.decode, encode=a.encode, sample=a.sample)
+                     on_error='skip', decode=a.decode, encode=a.encode, sample=a.sample,
+                     **({'device_formats': a.device_formats} if a.device_formats != 'strips'
+                        else {}))
         t = {}
         files = None
         for step in ('setup', 'parse', 'analyze', 'output'):
@@ -251,9 +281,12 @@ def main():
         nb = len(j.stack['band_numbers'])
         decoded = K * nb * P * 2  # the int16 bands ingested per acquisition (two without a mask_eqn)
         out_bytes = sum(os.path.getsize(p) for v in files.values() for p in v)
-        res = {'workload': 'job: %d x %d px x %d acquisitions, 2 int16 bands each (LZW GeoTIFF), '
+        res = {'workload': 'job: %d x %d px x %d acquisitions, 2 int16 bands each (%s GeoTIFF, %s), '
                            "index_eqn 'B1 - B2', line_cost 10, one GD rule%s"
-                           % (a.rows, a.cols, K, ', per-year trendline rasters' if a.trendline
+                           % (a.rows, a.cols, K, a.compress.upper() if a.compress == 'lzw'
+                              else 'Deflate',
+                              '%d x %d tiles' % (a.tiff_tile, a.tiff_tile) if a.tiff_tile
+                              else 'strips', ', per-year trendline rasters' if a.trendline
                               else ''),
                'pixels': P, 'acquisitions': K, 'host_threads': host_threads(),
                'input_bytes': in_bytes, 'generate_s': round(gen_s, 2),
@@ -268,7 +301,8 @@ def main():
                'analyze_parts_s': {k: round(v, 3) for k, v in getattr(j, 'analyze_s', {}).items()},
                'upload': os.environ.get('LT_JOB_UPLOAD', 'whole'),
                'decode': a.decode, 'decode_stats': j.decode_stats,
-               'sample': a.sample, 'shift': a.shift, 'mask': a.mask,
+               'compress': a.compress, 'tiff_tile': a.tiff_tile,
+               'device_formats': a.device_formats, 'sample': a.sample, 'shift': a.shift, 'mask': a.mask,
                'sample_stats': j.sample_stats,
                'encode': a.encode, 'encode_stats': j.encode_stats,
                'decode_times_s': {k: round(v, 3)
