@@ -353,6 +353,44 @@ int lt_analyze_tiles_ev(lt_ctx* ctx, const lt_scene* scene, const lt_params* par
 int lt_label_tile(lt_ctx* ctx, const lt_label_in* in, const lt_params* params,
                   const lt_tile_out* out, void* stream);
 
+/* ---- fit to vertex (FTV; an added export of ABI 8) ------------------------------------------------
+ * The spikes and vertices an analysis found on one index, applied to a second index: the standard
+ * LandTrendr product "segment with NBR, read wetness fitted at the same vertices". Input: the
+ * winner / spike / vertex planes as lt_analyze_* wrote them and the second index's value of every
+ * observation (one of obs_val / obs_index). Every pointer is a DEVICE pointer. */
+typedef struct {
+  int64_t n_pix;
+  int64_t stride;          /* elements between the year planes of winner / spike / vertex */
+  const int16_t* winner;   /* [Y][stride] DEVICE, as lt_analyze_* wrote them */
+  const uint8_t* spike;
+  const uint8_t* vertex;
+  int64_t obs_stride;      /* elements between observation planes of the values (>= n_pix) */
+  const double* obs_val;   /* [K][obs_stride], or NULL */
+  const void* obs_index;   /* [K][obs_stride] in index_type (what lt_index_apply wrote), or NULL */
+  int32_t index_type;      /* LT_T_* */
+  int32_t _pad;
+} lt_ftv_in;
+/* vertices2eqns (utils.py:646-669) and eqns2fitted_points (utils.py:682-722) per pixel, bit for
+ * bit, on given planes (land_trendr_amd/csrc/lt_ftv.h; one wave per 64 pixels, the fits in
+ * lockstep over the context's x-set table), asynchronous on `stream`:
+ *   present slots: winner[y] >= 0 (T of them); x(y) = year[y] - year[first present slot];
+ *   val_raw[y] = the value of obs winner[y] (spikes included), NaN for absent slots;
+ *   T == 0 / T == 1: status LT_ST_EMPTY / LT_ST_SINGLE_YEAR, every fit field NaN;
+ *   else the non-spike present points are the fitting series, its flagged points the vertices,
+ *   segment q the emulated-dgelsd least squares over the points from vertex q to vertex q+1
+ *   inclusive (the last vertex takes the last segment's), and val_fit / fit_m / fit_b / right_m /
+ *   right_b follow as in lt_analyze_*; LT_ST_NUMERIC is set when a fit fails.
+ * Writes out->val_raw, val_fit, fit_m, fit_b, right_m, right_b ([Y][out->stride]) and out->status,
+ * each only if non-NULL; every other field of `out` is ignored. Of `scene` only n_obs, n_years and
+ * year are read. Malformed planes (fewer than two vertices with T >= 2; a winner outside
+ * [-1, n_obs), which counts as absent) set LT_ST_NUMERIC, leave the fit values unspecified and
+ * never read or write out of bounds. LT_ERR_ARG, with nothing launched, for a null scene / in /
+ * out, null flag planes with n_pix > 0 and n_years > 0, stride, obs_stride or out->stride below
+ * n_pix, both or neither of obs_val / obs_index, and an index_type that is no raster type;
+ * LT_ERR_LIMIT as lt_analyze_tile gives it for the scene; LT_OK at once for n_pix == 0. */
+int lt_ftv_tile(lt_ctx* ctx, const lt_scene* scene, const lt_ftv_in* in, const lt_tile_out* out,
+                void* stream);
+
 /* Output raster assembly: n_jobs rasters (lt_raster_job), asynchronous on `stream`: a fill of
  * every raster pixel with NODATA's converted value, then the selected grid points scattered in
  * (one pass when dest is NULL). Replaces data2raster's per-point loop (utils.py:429-438) and the

@@ -226,6 +226,17 @@ class LtLabelIn(ctypes.Structure):
                 ('vertex', c_u8p), ('present', c_u8p)]
 
 
+class LtFtvIn(ctypes.Structure):
+    """lt_ftv_in: the planes of an analysis and a second index's values (lt_ftv_tile)."""
+    _fields_ = [('n_pix', ctypes.c_int64), ('stride', ctypes.c_int64), ('winner', c_i16p),
+                ('spike', c_u8p), ('vertex', c_u8p), ('obs_stride', ctypes.c_int64),
+                ('obs_val', c_f64p), ('obs_index', ctypes.c_void_p),
+                ('index_type', ctypes.c_int32), ('_pad', ctypes.c_int32)]
+
+
+# the planes lt_ftv_tile writes (besides status)
+FTV_FIELDS = ('val_raw', 'val_fit', 'fit_m', 'fit_b', 'right_m', 'right_b')
+
 # per-year outputs [Y][stride] and per-rule outputs [R][stride]: (field, numpy dtype)
 YEAR_FIELDS = [('winner', 'int16'), ('val_raw', 'float64'), ('val_fit', 'float64'),
                ('fit_m', 'float64'), ('fit_b', 'float64'), ('right_m', 'float64'),
@@ -242,7 +253,7 @@ EXPORTS = ['lt_abi_version', 'lt_ctx_create', 'lt_ctx_destroy', 'lt_last_error',
            'lt_index_linearize', 'lt_ctx_set_jit_mode', 'lt_jit_prepare', 'lt_ctx_jit_stats',
            'lt_jit_source', 'lt_analyze_tiles_ev', 'lt_tiff_decode_strips_dev',
            'lt_tiff_encode_strips_dev', 'lt_grid_sample_dev', 'lt_mask_codegen',
-           'lt_mask_compile', 'lt_mask_apply', 'lt_tiff_decode_chunks_dev']
+           'lt_mask_compile', 'lt_mask_apply', 'lt_tiff_decode_chunks_dev', 'lt_ftv_tile']
 
 LT_JIT_SYNC, LT_JIT_ASYNC = 0, 1
 LT_JIT_SRC_SPEC, LT_JIT_SRC_SCENE, LT_JIT_SRC_FIELDS = 1, 2, 4
@@ -292,6 +303,8 @@ def load_lib(path=None):
                                         ctypes.POINTER(vp), ctypes.c_int32, vp]
     lib.lt_label_tile.argtypes = [vp, ctypes.POINTER(LtLabelIn), ctypes.POINTER(LtParams),
                                   ctypes.POINTER(LtTileOut), vp]
+    lib.lt_ftv_tile.argtypes = [vp, ctypes.POINTER(LtScene), ctypes.POINTER(LtFtvIn),
+                                ctypes.POINTER(LtTileOut), vp]
     lib.lt_ctx_set_timing.argtypes = [vp, ctypes.c_int]
     lib.lt_ctx_stage_ms.argtypes = [vp, c_f64p, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]
     lib.lt_ctx_last_deferred.argtypes = [vp, ctypes.POINTER(ctypes.c_int64)]

@@ -325,6 +325,7 @@ DecodeScratch& ctx_decode(lt_ctx* c) { return c->dec; }
 EncodeScratch& ctx_encode(lt_ctx* c) { return c->enc; }
 ChunkScratch& ctx_chunks(lt_ctx* c) { return c->chk; }
 int ctx_device(const lt_ctx* c) { return c->device; }
+const lsq_xf* ctx_xtab(const lt_ctx* c) { return c->d_xtab; }
 int ctx_fail(lt_ctx* c, int code, const char* fmt, const char* detail) {
   return fail(c, code, fmt, detail);
 }

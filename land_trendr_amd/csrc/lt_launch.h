@@ -84,6 +84,8 @@ DecodeScratch& ctx_decode(lt_ctx* c);
 EncodeScratch& ctx_encode(lt_ctx* c);
 ChunkScratch& ctx_chunks(lt_ctx* c);
 int ctx_device(const lt_ctx* c);
+// the context's x-set factor table (lt_lapack.h), as the fit-to-vertex kernel reads it (lt_ftv.hip)
+const lsq_xf* ctx_xtab(const lt_ctx* c);
 int ctx_fail(lt_ctx* c, int code, const char* fmt, const char* detail);
 
 // Stage 1: the analyze kernel over every pixel of the tile, on l.stream.

@@ -14,6 +14,7 @@ TRENDLINE = tuple(f for f, _ in _abi.YEAR_FIELDS)
 LABELS = tuple(f for f, _ in _abi.RULE_FIELDS)
 ALL_FIELDS = TRENDLINE + LABELS + ('status', 'n_years')
 LABEL_FIELDS = ('status', 'matched', 'class_val', 'onset_year', 'duration', 'magnitude')
+FTV_FIELDS = _abi.FTV_FIELDS  # the planes ftv_tile writes (besides status)
 
 _DT = {'int16': torch.int16, 'int32': torch.int32, 'uint8': torch.uint8,
        'float64': torch.float64}
@@ -225,6 +226,85 @@ class Engine:
         for f, t in out.items():
             setattr(tout, f, ctypes.cast(t.data_ptr(), type(getattr(tout, f))))
         return tin, tout, out
+
+    # --- fit to vertex: an analysis's segments on a second index (lt_ftv_tile, lt_ftv.hip) ---
+    def ftv_tile(self, scene, winner, spike, vertex, values, fields=FTV_FIELDS, out=None,
+                 stream=None):
+        """The spikes and vertices of an analysis applied to a second index (vertices2eqns +
+        eqns2fitted_points on given planes). winner int16 / spike uint8 / vertex uint8: [Y, P]
+        tensors as analyze_tile wrote them, unit pixel stride, one shared row stride >= P.
+        values: [K, P] float64, or an index raster in its stored type (what index_tile writes).
+        Returns the dict of device tensors: the requested `fields` of FTV_FIELDS ([Y, P]
+        float64) and 'status' ([P] int32); asynchronous on `stream`. out: tensors to fill instead
+        (exactly the planes to write: [Y, >= P] float64 sharing one row stride, 'status' [>= P])."""
+        Y, K = scene.n_years, scene.n_obs
+        if (not isinstance(winner, torch.Tensor) or winner.dim() != 2 or
+                winner.dtype != torch.int16 or winner.device != self.device or
+                winner.shape[0] != Y or (winner.shape[1] > 1 and winner.stride(1) != 1)):
+            raise LtError('winner must be an int16 [%d, P] tensor on %s with unit pixel stride'
+                          % (Y, self.device))
+        P = winner.shape[1]
+        istride = winner.stride(0) if Y > 1 else max(P, 1)
+        if istride < P:
+            raise LtError('winner rows must not overlap')
+        for name, t in (('spike', spike), ('vertex', vertex)):
+            if (not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or
+                    t.device != self.device or t.shape != winner.shape or
+                    (P > 1 and t.stride(1) != 1) or (Y > 1 and t.stride(0) != istride)):
+                raise LtError('%s must be uint8 with the shape and row stride of winner' % name)
+        if (not isinstance(values, torch.Tensor) or values.dtype not in _LT_T or
+                values.device != self.device or values.dim() != 2 or
+                tuple(values.shape) != (K, P) or (P > 1 and values.stride(1) != 1)):
+            raise LtError('values must be a [%d, %d] raster tensor on %s with unit pixel stride'
+                          % (K, P, self.device))
+        vstride = values.stride(0) if K > 1 else max(P, 1)
+        if vstride < P:
+            raise LtError('values rows must not overlap')
+        if out is None:
+            bad = [f for f in fields if f not in FTV_FIELDS]
+            if bad:
+                raise LtError('ftv_tile writes %s, not %s' % (', '.join(FTV_FIELDS), bad))
+            out = self.alloc_outputs(Y, 0, P, tuple(fields) + ('status',))
+        ostride = None
+        for f, t in out.items():
+            if f not in FTV_FIELDS and f != 'status':
+                raise LtError('ftv_tile writes %s and status, not %s' % (', '.join(FTV_FIELDS), f))
+            if (not isinstance(t, torch.Tensor) or t.device != self.device or
+                    t.dtype != _DTYPE[f] or t.shape[-1] < P):
+                raise LtError('output %s has wrong device/dtype/shape' % f)
+            if f == 'status':
+                if t.dim() != 1 or (t.numel() > 1 and t.stride(0) != 1):
+                    raise LtError('output status must be a [P] tensor with unit stride')
+                continue
+            if t.dim() != 2 or t.shape[0] < Y or (t.shape[1] > 1 and t.stride(1) != 1):
+                raise LtError('output %s too small' % f)
+            s = t.stride(0) if t.shape[0] > 1 else max(P, 1)
+            if s < P:
+                raise LtError('output %s rows must not overlap' % f)
+            if ostride is None:
+                ostride = s
+            elif s != ostride:
+                raise LtError('all [Y, P] outputs must share one row stride')
+        fin = _abi.LtFtvIn()
+        fin.n_pix, fin.stride, fin.obs_stride = P, istride, vstride
+        fin.winner = ctypes.cast(winner.data_ptr(), _abi.c_i16p)
+        fin.spike = ctypes.cast(spike.data_ptr(), _abi.c_u8p)
+        fin.vertex = ctypes.cast(vertex.data_ptr(), _abi.c_u8p)
+        if values.dtype == torch.float64:
+            fin.obs_val = ctypes.cast(values.data_ptr(), _abi.c_f64p)
+        else:
+            fin.obs_index = values.data_ptr()
+            fin.index_type = _LT_T[values.dtype]
+        tout = _abi.LtTileOut()
+        tout.stride = ostride if ostride is not None else max(P, 1)
+        for f, t in out.items():
+            setattr(tout, f, ctypes.cast(t.data_ptr(), type(getattr(tout, f))))
+        sc = scene.to_c()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        rc = self.lib.lt_ftv_tile(self.ctx, ctypes.byref(sc), ctypes.byref(fin),
+                                  ctypes.byref(tout), ctypes.c_void_p(st.cuda_stream))
+        self._check(rc, 'lt_ftv_tile')
+        return out
 
     # --- load stage: index_eqn (rast_algebra, utils.py:447-484) ---
     def compile_index(self, program):

@@ -21,7 +21,12 @@ Steps, as the reference chains them:
                                       to host memory per tile — a file-backed map shared by the
                                       ranks when there are several — never to one GPU);
   4. output   (output_reducer :128-152) raster.label_rasters / trendline_rasters placed by each
-                                      grid point's template offsets, written as GeoTIFFs.
+                                      grid point's template offsets, written as GeoTIFFs; with
+                                      settings.json ftv_eqns ({name: equation}; fit to vertex) also
+                                      'ftv/<name>/<date>-<attr>': each equation evaluated as
+                                      index_eqn would be and fitted at the analysis's vertices, one
+                                      pass per equation, one tile on the GPU at a time (one rank,
+                                      trendline=True).
 
 Multi-rank jobs: rank 0 alone extracts the compressed rasters and writes the grid, then every rank
 reads them (a barrier between), so no rank sees a partial extraction or a truncated grid.
@@ -180,6 +185,29 @@ class LocalJob:
         self._raster_hw = None   # (rows, cols) of the raster order, or None
         self.raster_grid = None  # (geotransform, rows, cols) of the raster order, or None
         self._grid_axes = None   # (x of each grid column, y of each grid row) of the raster order
+        # settings.json ftv_eqns (fit to vertex): {name: seconds of its pass} once output() ran
+        self.ftv_s = {}
+        if os.path.exists(self.settings_path):  # what the job cannot do is said at construction
+            try:
+                with open(self.settings_path) as f:
+                    peek = json.load(f)
+            except ValueError:
+                peek = None  # (setup() reports a settings.json that does not parse)
+            if isinstance(peek, dict):
+                self._check_ftv(peek)
+
+    def _check_ftv(self, settings):
+        """settings.json ftv_eqns: validated (settings.check_ftv_eqns), and supported by a job of
+        one rank that keeps the trendline planes; ValueError otherwise."""
+        from .settings import check_ftv_eqns
+        if not check_ftv_eqns(settings).get('ftv_eqns'):
+            return
+        if not self.trendline:
+            raise ValueError('ftv_eqns needs trendline=True: the fit-to-vertex pass reads the '
+                             "analysis's winner / spike / vertex planes")
+        if self._dist()[1] > 1:
+            raise ValueError('ftv_eqns is supported on one rank only (world size %d): the '
+                             'fit-to-vertex pass is not distributed' % self._dist()[1])
 
     @property
     def grid_fn(self):
@@ -262,6 +290,7 @@ class LocalJob:
             self.grid_xy = grid_coords(self.rast_fns[0])
         with open(self.settings_path) as f:
             self.settings = json.load(f)
+        self._check_ftv(self.settings)
         return self.rast_fns
 
     def _internal_order(self):
@@ -319,9 +348,11 @@ class LocalJob:
         P = len(self.grid_xy[0])
         self.mosaic = Mosaic([P], self.tile_pixels, world, rank, 'round_robin')
         # the planes ingested: the bands of index_eqn and, if set, of mask_eqn (the reference's
-        # all_bands, utils.py:459-461)
+        # all_bands, utils.py:459-461) and of every fit-to-vertex equation (ftv_eqns)
         eqn_bands = sorted(set(parse_eqn_bands(self.settings['index_eqn'])) |
-                           set(parse_eqn_bands(self.settings.get('mask_eqn') or '')))
+                           set(parse_eqn_bands(self.settings.get('mask_eqn') or '')) |
+                           {b for e in (self.settings.get('ftv_eqns') or {}).values()
+                            for b in parse_eqn_bands(e)})
         # on a GPU (LT_JOB_UPLOAD=whole), each raster's planes cross to the device as soon as they
         # are decoded, on the worker that decoded them, while the other rasters decode: analyze()
         # then starts from the device stack
@@ -863,7 +894,7 @@ class LocalJob:
         finished GDT_Byte (or typed) array, written at once; a grid that maps two points to one
         pixel (the reference's loop: the last one wins) is assembled on the host."""
         import torch
-        from .raster import (_np_dtype, _strip_rows, device_encodable, label_rasters,
+        from .raster import (FTV_ATTRS, _np_dtype, _strip_rows, device_encodable, label_rasters,
                              label_rasters_device, output_reducer, raster_path,
                              trendline_rasters, trendline_rasters_device, write_tiff_strips)
         tmpl = GeoTiff(self.rast_fns[0])
@@ -976,6 +1007,14 @@ class LocalJob:
                     trendline_rasters_device(self.engine, rows_dev, self.scene, self.scene.dates,
                                              (rows, cols), ddest, tdt, self.raster_mode,
                                              sink=write, device_sink=dsink)
+                    # fit to vertex: one equation's planes at a time (the host planes are reused)
+                    for name, fhost in self._ftv_passes():
+                        trendline_rasters_device(
+                            self.engine, _DeviceRows(fhost, dp['status'].device, rows_dev.winner),
+                            self.scene, self.scene.dates, (rows, cols), ddest, tdt,
+                            self.raster_mode, attrs=FTV_ATTRS, sink=write, device_sink=dsink,
+                            prefix='ftv/%s/' % name)
+                        settle(0)  # every raster of the equation is written: its planes are free
                 settle(0)
             finally:
                 writer.shutdown(wait=True)
@@ -994,9 +1033,63 @@ class LocalJob:
             rasters.update(trendline_rasters(placed, self.scene, self.scene.dates, (rows, cols),
                                              tdt, self.raster_mode))
         res = dict(output_reducer(rasters, tmpl, self.root, self.job))
+        if self.trendline:
+            for name, fhost in self._ftv_passes():
+                fplaced = {'winner': placed['winner']}
+                for k, a in fhost.items():
+                    b = np.zeros(a.shape[:-1] + (n,), a.dtype)
+                    b[..., dest] = a
+                    fplaced[k] = b
+                res.update(output_reducer(
+                    trendline_rasters(fplaced, self.scene, self.scene.dates, (rows, cols), tdt,
+                                      self.raster_mode, attrs=FTV_ATTRS, prefix='ftv/%s/' % name),
+                    tmpl, self.root, self.job))
         self.encode_stats = {'device': 0, 'host': len(res)}
         self._join_grid()
         return res
+
+    def _ftv_passes(self):
+        """settings.json ftv_eqns after the analysis: for each equation in turn, yields (name, its
+        host planes {field: [Y, P] float64}): the equation evaluated as index_eqn would be
+        (Engine.index_tile) and fitted to the analysis's vertices (Engine.ftv_tile), the tiles one
+        at a time — a tile's winner / spike / vertex rows go up from the host trendline planes, its
+        six planes come down — so the device never holds more than one tile of FTV planes. The
+        host planes are reused by the next equation: the caller is done with them before it asks
+        for the next. A pixel the analysis rejected has no winner there (_check_errors), so it gets
+        no FTV raster either."""
+        eqns = self.settings.get('ftv_eqns') or {}
+        if not eqns:
+            return
+        import torch
+        from .engine import FTV_FIELDS
+        from .index_eqn import IndexProgram
+        eng = self.engine
+        if not hasattr(eng, 'ftv_tile'):
+            raise RuntimeError('ftv_eqns needs the HIP engine (no CPU path exists)')
+        dev = torch.device(eng.device)
+        st, tl = self.stack, self.host_trendline
+        numbers = list(st['band_numbers'])
+        b_dtype = self._stack_meta[0] if self._stack_meta is not None else st['bands'].dtype
+        Y, P = self.scene.n_years, st['n_pix']
+        host = {f: np.empty((Y, P), np.float64) for f in FTV_FIELDS}
+        nmax = max([t.n for t in self.mosaic.mine] + [1])
+        buf = torch.empty((len(FTV_FIELDS), Y, nmax), dtype=torch.float64, device=dev)
+        for name, eqn in eqns.items():
+            t0 = time.perf_counter()
+            prog = IndexProgram(eqn, band_dtype=b_dtype, raster_count=max(numbers))
+            slots = [numbers.index(b) for b in prog.bands]  # the planes the equation reads
+            fn = eng.compile_index(prog)
+            for t in self.mosaic.mine:
+                flags = [torch.from_numpy(np.ascontiguousarray(tl[f][:, t.p0:t.p1])).to(dev)
+                         for f in ('winner', 'spike', 'vertex')]
+                t_bands, _ = stack_range(st, t.p0, t.p1)
+                bands = torch.from_numpy(np.ascontiguousarray(t_bands[:, slots])).to(dev)
+                out = {f: buf[i, :, :t.n] for i, f in enumerate(FTV_FIELDS)}
+                eng.ftv_tile(self.scene, *flags, eng.index_tile(fn, bands), out=out)
+                for f, o in out.items():
+                    host[f][:, t.p0:t.p1] = o.cpu().numpy()
+            self.ftv_s[name] = time.perf_counter() - t0
+            yield name, host
 
     def run(self):
         """Every rank runs setup/parse/analysis; the writer (rank 0) also writes the rasters.
@@ -1017,10 +1110,12 @@ class _DeviceRows:
     uploaded into a buffer of its own when the row is asked for (the rows of one date's rasters
     are assembled together, then the next date's rows overwrite them in stream order)."""
 
-    def __init__(self, host, device):
+    def __init__(self, host, device, winner=None):
         import torch
         self.host, self.device = host, device
-        self.winner = torch.from_numpy(np.ascontiguousarray(host['winner'])).to(device)
+        # (winner: the device plane another _DeviceRows of the same analysis already holds)
+        self.winner = winner if winner is not None else torch.from_numpy(
+            np.ascontiguousarray(host['winner'])).to(device)
         self.buf = {}
 
     def __getitem__(self, field):

@@ -31,6 +31,8 @@ NODATA = _abi.LT_NODATA  # settings.py:16
 LABEL_KEYS = ('class_val', 'onset_year', 'magnitude', 'duration')
 TRENDLINE_ATTRS = ('val_raw', 'val_fit', 'eqn_fit_slope', 'eqn_fit_intercept', 'eqn_right_slope',
                    'eqn_right_intercept', 'spike', 'vertex')
+# the six binary64 attributes: what a fit-to-vertex equation's rasters carry ('ftv/<name>/...')
+FTV_ATTRS = TRENDLINE_ATTRS[:6]
 _PLANE_OF_ATTR = {'val_raw': 'val_raw', 'val_fit': 'val_fit', 'eqn_fit_slope': 'fit_m',
                   'eqn_fit_intercept': 'fit_b', 'eqn_right_slope': 'right_m',
                   'eqn_right_intercept': 'right_b', 'spike': 'spike', 'vertex': 'vertex'}
@@ -88,10 +90,11 @@ def label_rasters(out, rules, shape, template_dtype=np.int16, mode='reference'):
 
 
 def trendline_rasters(out, scene, dates, shape, template_dtype=np.int16, mode='reference',
-                      attrs=TRENDLINE_ATTRS):
+                      attrs=TRENDLINE_ATTRS, prefix='trendline/'):
     """Per winning acquisition date d and attribute a, the raster 'trendline/<d>-<a>': the pixels
     whose winner in d's year is d carry the attribute, all others NODATA (the reference's
-    mr_label_output keys, classes.py:100-116, reduced per key)."""
+    mr_label_output keys, classes.py:100-116, reduced per key). prefix: the keys' first part
+    instead of 'trendline/' (a fit-to-vertex equation's rasters: 'ftv/<name>/', attrs FTV_ATTRS)."""
     rows, cols = shape
     n = rows * cols
     winner = _np(out['winner'])
@@ -105,7 +108,7 @@ def trendline_rasters(out, scene, dates, shape, template_dtype=np.int16, mode='r
                 plane = _np(out[_PLANE_OF_ATTR[a]])[y, :n].reshape(rows, cols)
                 if a in ('spike', 'vertex'):
                     plane = plane.astype(np.int64)  # mr_label_output emits 1 / 0 (classes.py:107)
-                key = 'trendline/%s-%s' % (d, a)
+                key = '%s%s-%s' % (prefix, d, a)
                 if mode == 'typed':
                     typ = np.uint8 if a in ('spike', 'vertex') else np.float64
                     r = np.full((rows, cols), NODATA, np.float64)
@@ -440,13 +443,14 @@ def label_rasters_device(engine, planes, rules, shape, dest=None, template_dtype
 
 def trendline_rasters_device(engine, planes, scene, dates, shape, dest=None,
                              template_dtype=np.int16, mode='reference', attrs=TRENDLINE_ATTRS,
-                             sink=None, device_sink=None):
+                             sink=None, device_sink=None, prefix='trendline/'):
     """trendline_rasters for [Y, P] planes in device memory: the winning acquisition dates come
     from lt_winner_presence, each 'trendline/<date>-<attr>' raster from lt_raster_assemble, one
     year slot at a time; sink(key, array) receives each raster as it reaches the host (default:
     collected into the returned dict). device_sink: when given, each date's assembled rasters go
     to device_sink([(key, [rows, cols] device tensor), ...]) in one batch instead and nothing is
-    copied down here. Dates shared by two observations fall back to the host."""
+    copied down here. Dates shared by two observations fall back to the host. prefix: as
+    trendline_rasters."""
     import ctypes
     import torch
     from .index_eqn import DTYPES
@@ -488,7 +492,7 @@ def trendline_rasters_device(engine, planes, scene, dates, shape, dest=None,
             if not ref and a in ('spike', 'vertex'):
                 j.fill = 0.0
             jobs.append(j)
-            outs.append(('trendline/%s-%s' % (names[o], a), out))
+            outs.append(('%s%s-%s' % (prefix, names[o], a), out))
         engine.raster_assemble(jobs)
         if device_sink is not None:
             device_sink([(key, out.view(rows, cols)) for key, out in outs])

@@ -16,12 +16,13 @@ import torch
 
 from . import _abi
 from .classes import Disturbance, LabelRule, Trendline, TrendlinePoint
-from .engine import ALL_FIELDS, LABELS, get_engine, label_tile
+from .engine import ALL_FIELDS, FTV_FIELDS, LABELS, get_engine, label_tile
 from .scene import build_scene, parse_date
 from .settings import compile_params, load_settings
 
 __all__ = ['parse_date', 'analyze', 'change_labeling', 'analysis_reducer',
-           'analysis_reducer_batch', 'analyze_tile', 'index_tile', 'match_rules_gpu']
+           'analysis_reducer_batch', 'analyze_tile', 'index_tile', 'match_rules_gpu',
+           'fit_to_vertices_tile']
 
 
 def _raise_for_status(status, n_obs_valid):
@@ -39,6 +40,14 @@ def _raise_for_status(status, n_obs_valid):
 def analyze_tile(scene, params, values, valid=None, fields=ALL_FIELDS, out=None, device=None):
     """Batched analyze + label of a pixel tile on the GPU (see Engine.analyze_tile)."""
     return get_engine(device).analyze_tile(scene, params, values, valid, fields, out)
+
+
+def fit_to_vertices_tile(scene, winner, spike, vertex, values, fields=FTV_FIELDS, out=None,
+                         device=None):
+    """Fit to vertex on the GPU: the winner / spike / vertex planes of an analysis ([Y, P]) and a
+    second index's values ([K, P]) -> that index's trendline planes at the same vertices
+    (vertices2eqns + eqns2fitted_points, utils.py:646-722; see Engine.ftv_tile)."""
+    return get_engine(device).ftv_tile(scene, winner, spike, vertex, values, fields, out)
 
 
 def analyze(pix_datas, line_cost, target_date):
@@ -141,7 +150,12 @@ def analysis_reducer_batch(dates, values, valid, settings, fields=LABELS + ('sta
     settings['index_eqn'] is then evaluated on the GPU first (parse_mapper's rast_algebra,
     mr_land_trendr_job.py:67-68). band_numbers: the reference band number of each plane (default
     1..n_bands). settings['mask_eqn'], if present, is evaluated on the same planes and ANDed into
-    a copy of valid (all ones when valid is None): the caller's tensor is not modified."""
+    a copy of valid (all ones when valid is None): the caller's tensor is not modified.
+
+    settings['ftv_eqns'] ({name: equation}; needs bands): when the trendline planes winner,
+    spike and vertex are among `fields`, every equation is evaluated on the bands as index_eqn
+    would be and fitted to the analysis's vertices; out['ftv'][name][field] holds its FTV_FIELDS
+    planes and its 'status'."""
     settings = load_settings(settings)
     scene = build_scene(dates, parse_date(settings['target_date']))
     params, rules = compile_params(settings['line_cost'], settings.get('label_rules', ()),
@@ -151,6 +165,14 @@ def analysis_reducer_batch(dates, values, valid, settings, fields=LABELS + ('sta
             valid = mask_tile(settings['mask_eqn'], bands, valid, band_numbers, device=device)
         values = index_tile(settings['index_eqn'], bands, band_numbers, device=device)
     out = analyze_tile(scene, params, values, valid, fields, device=device)
+    if settings.get('ftv_eqns') and all(f in out for f in ('winner', 'spike', 'vertex')):
+        if bands is None:
+            raise ValueError('ftv_eqns needs the band planes (bands=...)')
+        out['ftv'] = {
+            name: fit_to_vertices_tile(scene, out['winner'], out['spike'], out['vertex'],
+                                       index_tile(eqn, bands, band_numbers, device=device),
+                                       device=device)
+            for name, eqn in settings['ftv_eqns'].items()}
     out['_scene'] = scene
     out['_rules'] = rules
     return out

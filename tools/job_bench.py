@@ -16,7 +16,11 @@ would, on cuda:0, and the script prints one JSON line:
     python tools/job_bench.py --rows 7000 --cols 7000 --years 30 [--trendline] [--check 20000]
                               [--decode {host,device}] [--encode {host,device}]
                               [--sample {host,device}] [--shift N] [--mask PROB]
-                              [--mask-eqn EQN | --qa-cloudmask]
+                              [--mask-eqn EQN | --qa-cloudmask] [--ftv EQN]
+
+--ftv EQN (needs --trendline): settings.json gets ftv_eqns {'ftv': EQN} (e.g. 'B1'), so the output
+step also runs the fit-to-vertex pass for that equation and writes its 'ftv/ftv/<date>-<attr>'
+rasters; the line reports the pass's seconds (LocalJob.ftv_s).
 
 --mask-eqn EQN: the rasters carry a third band, a QA band that is 0 with the --mask probability
 and 1 elsewhere, instead of cloudmask rasters; settings.json gets mask_eqn EQN (e.g. 'B3 != 0') and
@@ -219,6 +223,9 @@ def main():
     ap.add_argument('--device-formats', default='strips', choices=('strips', 'all'),
                     help="what --decode device offers the GPU (LocalJob device_formats=): 'strips' "
                          "uncompressed / LZW strip files, 'all' tiles and Deflate as well")
+    ap.add_argument('--ftv', default=None,
+                    help="settings.json ftv_eqns {'ftv': EQN} (e.g. 'B1'): the fit-to-vertex pass "
+                         'of one equation in the output step (needs --trendline)')
     ap.add_argument('--reuse', action='store_true',
                     help='use the stack an earlier --keep run left in --work (written with the '
                          'same size and format options) instead of writing it again: runs that '
@@ -248,6 +255,16 @@ def main():
                                             (a.tiff_tile, a.tiff_tile) if a.tiff_tile else None)
         print('stack written: %.1f s, %.2f GB' % (gen_s, in_bytes / 1e9), file=sys.stderr,
               flush=True)
+        spath = os.path.join(a.work, 'bench', 'input', 'settings.json')
+        with open(spath) as f:
+            settings = json.load(f)
+        settings.pop('ftv_eqns', None)  # (a reused stack's settings may carry an earlier run's)
+        if a.ftv:
+            if not a.trendline:
+                ap.error('--ftv needs --trendline')
+            settings['ftv_eqns'] = {'ftv': a.ftv}
+        with open(spath, 'w') as f:
+            json.dump(settings, f)
         P = a.rows * a.cols
         j = LocalJob(a.work, 'bench', device=0, tile_pixels=a.tile, trendline=a.trendline,
                      on_error='skip', decode=a.decode, encode=a.encode, sample=a.sample,
@@ -319,6 +336,9 @@ def main():
                 nbytes = K * P * (2 * n_slots + 2)
                 res['mask_pass'] = {'ms': round(ms * 1e3, 4), 'bytes': nbytes,
                                     'tb_per_s': round(nbytes / ms / 1e12, 4)}
+        if a.ftv:
+            res['ftv_eqn'] = a.ftv
+            res['ftv_pass_s'] = {k: round(v, 3) for k, v in j.ftv_s.items()}
         if a.diag:
             res['diag'] = diag(j)
         if a.check > 0:
