@@ -234,6 +234,24 @@ class LtFtvIn(ctypes.Structure):
                 ('index_type', ctypes.c_int32), ('_pad', ctypes.c_int32)]
 
 
+class LtVertexIn(ctypes.Structure):
+    """lt_vertex_in: a trendline's per-year planes (lt_vertex_table)."""
+    _fields_ = [('n_pix', ctypes.c_int64), ('stride', ctypes.c_int64),
+                ('n_years', ctypes.c_int32), ('year', c_i32p), ('val_fit', c_f64p),
+                ('vertex', c_u8p), ('val_raw', c_f64p), ('present', c_u8p), ('winner', c_i16p)]
+
+
+class LtVertexOut(ctypes.Structure):
+    """lt_vertex_out: the vertex planes [V][stride] and the count [P] (lt_vertex_table)."""
+    _fields_ = [('stride', ctypes.c_int64), ('max_vertices', ctypes.c_int32),
+                ('n_vertices', c_i32p), ('vertex_year', c_i32p), ('vertex_fit', c_f64p),
+                ('vertex_raw', c_f64p)]
+
+
+# the planes lt_vertex_table writes: (field, numpy dtype); n_vertices is [P], the others [V, P]
+VERTEX_FIELDS = [('n_vertices', 'int32'), ('vertex_year', 'int32'), ('vertex_fit', 'float64'),
+                 ('vertex_raw', 'float64')]
+
 # the planes lt_ftv_tile writes (besides status)
 FTV_FIELDS = ('val_raw', 'val_fit', 'fit_m', 'fit_b', 'right_m', 'right_b')
 
@@ -253,7 +271,8 @@ EXPORTS = ['lt_abi_version', 'lt_ctx_create', 'lt_ctx_destroy', 'lt_last_error',
            'lt_index_linearize', 'lt_ctx_set_jit_mode', 'lt_jit_prepare', 'lt_ctx_jit_stats',
            'lt_jit_source', 'lt_analyze_tiles_ev', 'lt_tiff_decode_strips_dev',
            'lt_tiff_encode_strips_dev', 'lt_grid_sample_dev', 'lt_mask_codegen',
-           'lt_mask_compile', 'lt_mask_apply', 'lt_tiff_decode_chunks_dev', 'lt_ftv_tile']
+           'lt_mask_compile', 'lt_mask_apply', 'lt_tiff_decode_chunks_dev', 'lt_ftv_tile',
+           'lt_vertex_table']
 
 LT_JIT_SYNC, LT_JIT_ASYNC = 0, 1
 LT_JIT_SRC_SPEC, LT_JIT_SRC_SCENE, LT_JIT_SRC_FIELDS = 1, 2, 4
@@ -305,6 +324,8 @@ def load_lib(path=None):
                                   ctypes.POINTER(LtTileOut), vp]
     lib.lt_ftv_tile.argtypes = [vp, ctypes.POINTER(LtScene), ctypes.POINTER(LtFtvIn),
                                 ctypes.POINTER(LtTileOut), vp]
+    lib.lt_vertex_table.argtypes = [vp, ctypes.POINTER(LtVertexIn), ctypes.POINTER(LtVertexOut),
+                                    vp]
     lib.lt_ctx_set_timing.argtypes = [vp, ctypes.c_int]
     lib.lt_ctx_stage_ms.argtypes = [vp, c_f64p, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]
     lib.lt_ctx_last_deferred.argtypes = [vp, ctypes.POINTER(ctypes.c_int64)]

@@ -306,6 +306,94 @@ class Engine:
         self._check(rc, 'lt_ftv_tile')
         return out
 
+    # --- vertex table: a trendline as one row per vertex (lt_vertex_table, lt_vertex.hip) ---
+    def vertex_table(self, years, val_fit, vertex, present=None, winner=None, val_raw=None,
+                     max_vertices=None, out=None, stream=None):
+        """Each pixel's vertices compacted from its per-year planes. years: the calendar year of
+        each of the Y slots. val_fit float64 / vertex uint8: [Y, P] device tensors with unit
+        pixel stride and one shared row stride >= P; val_raw (float64), present (uint8, 0 = no
+        point in the slot) and winner (int16, a point iff >= 0) likewise, each optional, at most
+        one of present / winner. The first slot that holds a point is vertex 0, every later
+        flagged one the next. Returns the dict of device tensors: 'n_vertices' [P] int32 (the full
+        count), 'vertex_year' [V, P] int32, 'vertex_fit' [V, P] float64 and, with val_raw,
+        'vertex_raw' [V, P] float64, LT_NODATA from a pixel's count on; V = max_vertices
+        (default Y). out: tensors to fill instead (exactly the planes to write: [>= V, >= P]
+        sharing one row stride, of which V rows are written; 'n_vertices' [>= P]). Asynchronous
+        on `stream`."""
+        import numpy as np
+        if (not isinstance(val_fit, torch.Tensor) or val_fit.dim() != 2 or
+                val_fit.dtype != torch.float64 or val_fit.device != self.device or
+                (val_fit.shape[1] > 1 and val_fit.stride(1) != 1)):
+            raise LtError('val_fit must be a float64 [Y, P] tensor on %s with unit pixel stride'
+                          % self.device)
+        Y, P = val_fit.shape
+        istride = val_fit.stride(0) if Y > 1 else max(P, 1)
+        if istride < P:
+            raise LtError('val_fit rows must not overlap')
+        if present is not None and winner is not None:
+            raise LtError('at most one of present / winner')
+        for name, t, dt in (('vertex', vertex, torch.uint8), ('present', present, torch.uint8),
+                            ('winner', winner, torch.int16), ('val_raw', val_raw, torch.float64)):
+            if t is None and name != 'vertex':
+                continue
+            if (not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != self.device or
+                    t.shape != val_fit.shape or (P > 1 and t.stride(1) != 1) or
+                    (Y > 1 and t.stride(0) != istride)):
+                raise LtError('%s must be %s with the shape and row stride of val_fit'
+                              % (name, str(dt).split('.')[-1]))
+        yrs = np.ascontiguousarray(np.asarray(years, np.int32))
+        if yrs.ndim != 1 or len(yrs) != Y:
+            raise LtError('years must have one entry per slot')
+        if Y > _abi.LT_MAX_YEARS:
+            raise LtError('more than %d year slots' % _abi.LT_MAX_YEARS)
+        V = Y if max_vertices is None else int(max_vertices)
+        if not 1 <= V <= _abi.LT_MAX_YEARS:
+            raise LtError('max_vertices must be in [1, %d]' % _abi.LT_MAX_YEARS)
+        dts = {f: _DT[d] for f, d in _abi.VERTEX_FIELDS}
+        if out is None:
+            out = {f: torch.empty((P,) if f == 'n_vertices' else (V, P), dtype=dt,
+                                  device=self.device)
+                   for f, dt in dts.items() if f != 'vertex_raw' or val_raw is not None}
+        ostride = None
+        for f, t in out.items():
+            if f not in dts:
+                raise LtError('vertex_table writes %s, not %s' % (', '.join(dts), f))
+            if f == 'vertex_raw' and val_raw is None:
+                raise LtError('vertex_raw needs val_raw')
+            if (not isinstance(t, torch.Tensor) or t.device != self.device or
+                    t.dtype != dts[f] or t.shape[-1] < P):
+                raise LtError('output %s has wrong device/dtype/shape' % f)
+            if f == 'n_vertices':
+                if t.dim() != 1 or (t.numel() > 1 and t.stride(0) != 1):
+                    raise LtError('output n_vertices must be a [P] tensor with unit stride')
+                continue
+            if t.dim() != 2 or t.shape[0] < V or (t.shape[1] > 1 and t.stride(1) != 1):
+                raise LtError('output %s too small' % f)
+            s = t.stride(0) if t.shape[0] > 1 else max(P, 1)
+            if s < P:
+                raise LtError('output %s rows must not overlap' % f)
+            if ostride is None:
+                ostride = s
+            elif s != ostride:
+                raise LtError('all [V, P] outputs must share one row stride')
+        vin = _abi.LtVertexIn()
+        vin.n_pix, vin.stride, vin.n_years = P, istride, Y
+        vin.year = yrs.ctypes.data_as(_abi.c_i32p)
+        for f, t in (('val_fit', val_fit), ('vertex', vertex), ('val_raw', val_raw),
+                     ('present', present), ('winner', winner)):
+            if t is not None:
+                setattr(vin, f, ctypes.cast(t.data_ptr(), type(getattr(vin, f))))
+        vout = _abi.LtVertexOut()
+        vout.stride = ostride if ostride is not None else max(P, 1)
+        vout.max_vertices = V
+        for f, t in out.items():
+            setattr(vout, f, ctypes.cast(t.data_ptr(), type(getattr(vout, f))))
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        rc = self.lib.lt_vertex_table(self.ctx, ctypes.byref(vin), ctypes.byref(vout),
+                                      ctypes.c_void_p(st.cuda_stream))
+        self._check(rc, 'lt_vertex_table')
+        return out
+
     # --- load stage: index_eqn (rast_algebra, utils.py:447-484) ---
     def compile_index(self, program):
         """hiprtc-compile an index_eqn.IndexProgram for this device (cached per program). A

@@ -26,7 +26,12 @@ Steps, as the reference chains them:
                                       'ftv/<name>/<date>-<attr>': each equation evaluated as
                                       index_eqn would be and fitted at the analysis's vertices, one
                                       pass per equation, one tile on the GPU at a time (one rank,
-                                      trendline=True).
+                                      trendline=True); with settings.json vertex_table (true or
+                                      a cap on the vertices) also 'vertices/n_vertices' and
+                                      'vertices/<kk>-year', '<kk>-val_fit', '<kk>-val_raw': each
+                                      pixel's vertices, compacted on the GPU per tile (one rank;
+                                      trendline=True or False), and 'ftv/<name>/vertices/...' for
+                                      every fit-to-vertex equation.
 
 Multi-rank jobs: rank 0 alone extracts the compressed rasters and writes the grid, then every rank
 reads them (a barrier between), so no rank sees a partial extraction or a truncated grid.
@@ -187,6 +192,11 @@ class LocalJob:
         self._grid_axes = None   # (x of each grid column, y of each grid row) of the raster order
         # settings.json ftv_eqns (fit to vertex): {name: seconds of its pass} once output() ran
         self.ftv_s = {}
+        # settings.json vertex_table: the scene-wide vertex table on the analysis's device
+        # ({'n_vertices' [P], 'vertex_year' / 'vertex_fit' / 'vertex_raw' [V, P]}: 20 V + 4 bytes
+        # a pixel, kept there like the label planes) once analyze() has run; None without the key
+        self.vertex_planes = None
+        self._ftv_vertex = None  # the same for the fit-to-vertex equation output() is writing
         if os.path.exists(self.settings_path):  # what the job cannot do is said at construction
             try:
                 with open(self.settings_path) as f:
@@ -195,6 +205,7 @@ class LocalJob:
                 peek = None  # (setup() reports a settings.json that does not parse)
             if isinstance(peek, dict):
                 self._check_ftv(peek)
+                self._check_vertex(peek)
 
     def _check_ftv(self, settings):
         """settings.json ftv_eqns: validated (settings.check_ftv_eqns), and supported by a job of
@@ -208,6 +219,16 @@ class LocalJob:
         if self._dist()[1] > 1:
             raise ValueError('ftv_eqns is supported on one rank only (world size %d): the '
                              'fit-to-vertex pass is not distributed' % self._dist()[1])
+
+    def _check_vertex(self, settings):
+        """settings.json vertex_table: validated (settings.check_vertex_table), and supported by a
+        job of one rank; ValueError otherwise."""
+        from .settings import check_vertex_table
+        if 'vertex_table' not in check_vertex_table(settings):
+            return
+        if self._dist()[1] > 1:
+            raise ValueError('vertex_table is supported on one rank only (world size %d): the '
+                             'vertex table is not distributed' % self._dist()[1])
 
     @property
     def grid_fn(self):
@@ -291,6 +312,7 @@ class LocalJob:
         with open(self.settings_path) as f:
             self.settings = json.load(f)
         self._check_ftv(self.settings)
+        self._check_vertex(self.settings)
         return self.rast_fns
 
     def _internal_order(self):
@@ -615,7 +637,7 @@ class LocalJob:
         from .index_eqn import IndexProgram, MaskProgram
         from .runner import MosaicRunner, TileInput
         from .scene import build_scene, parse_date
-        from .settings import compile_params
+        from .settings import compile_params, vertex_cap
         st = self.stack
         P = st['n_pix']
         dist, world, rank = self._dist()
@@ -744,6 +766,28 @@ class LocalJob:
             if m_events:  # the mask kernels' time on the device
                 self.analyze_s['mask'] = sum(a.elapsed_time(b) for a, b in m_events) * 1e-3
         host = self.host_trendline = self._trendline_planes(tl_fields, Y, P, dist, world, rank)
+        # settings.json vertex_table: the tile's device planes gain what the table is made from
+        # (not streamed to the host unless the trendline is), and each tile's vertices are
+        # compacted (Engine.vertex_table) straight into scene-wide device planes [V, P] at the
+        # tile's offset: 20 V + 4 bytes a pixel that stay on the device like the label planes
+        V = vertex_cap(self.settings, Y)
+        vt_fields = tuple(f for f in ('val_raw', 'val_fit', 'vertex')
+                          if f not in tl_fields) if V is not None else ()
+        self.vertex_planes = vt = None
+        if V is not None:
+            if not hasattr(eng, 'vertex_table'):
+                raise RuntimeError('vertex_table needs the HIP engine (no CPU path exists)')
+            vt = self.vertex_planes = {
+                'n_vertices': torch.empty(P, dtype=torch.int32, device=dev),
+                'vertex_year': torch.empty((V, P), dtype=torch.int32, device=dev),
+                'vertex_fit': torch.empty((V, P), dtype=torch.float64, device=dev),
+                'vertex_raw': torch.empty((V, P), dtype=torch.float64, device=dev)}
+
+        def vertices(k):  # tile k's vertices, on the current stream, behind the tile's last stage
+            t, o = items[k].tile, runner.outs[k]
+            eng.vertex_table(self.scene.years, o['val_fit'][:, :t.n], o['vertex'][:, :t.n],
+                             winner=o['winner'][:, :t.n], val_raw=o['val_raw'][:, :t.n],
+                             max_vertices=V, out={f: a[..., t.p0:t.p1] for f, a in vt.items()})
         # the trendline planes: a ring of three tiles' buffers on the GPU (tile k reuses tile
         # k-3's once its rows have reached the host), so a rank's HBM never holds all its tiles'
         # trendlines
@@ -756,8 +800,8 @@ class LocalJob:
         # 'sync' — compile first (a disk-cached module loads at once)
         jit_mode = os.environ.get('LT_JOB_JIT', 'sync' if os.environ.get('LT_JOB_JIT_SYNC') == '1'
                                   else 'off')
-        runner = MosaicRunner(eng, m, params, items, label_fields + tl_fields, fn, dist,
-                              exchange_fields=label_fields, ring=3 if cuda else 0,
+        runner = MosaicRunner(eng, m, params, items, label_fields + tl_fields + vt_fields, fn,
+                              dist, exchange_fields=label_fields, ring=3 if cuda else 0,
                               jit=jit_mode != 'off')
         jit_async = cuda and runner.jit is not None and jit_mode == 'async'
         if jit_async:
@@ -796,10 +840,19 @@ class LocalJob:
             t = items[k].tile
             copied[k] = tls.push({f: runner.outs[k][f] for f in tl_fields}, t.n, t)
 
-        # tile k-1's rows are queued behind tile k's kernels, so the copies overlap them
+        # tile k-1's rows are queued behind tile k's kernels, so the copies overlap them; tile k's
+        # vertex table is queued first, behind its last stage (the step's calls are joined to the
+        # stream at one rank) and ahead of the event that reports its ring buffer free (recorded
+        # by push(k), after everything queued here)
+        def after(k):
+            if vt is not None:
+                vertices(k)
+            if k > 0:
+                push(k - 1)
+
         t_st = time.perf_counter()
         try:
-            runner.step(after_tile=(lambda k: push(k - 1) if k > 0 else None) if cuda else None,
+            runner.step(after_tile=after if cuda else None,
                         slab_free=copied.get if cuda else None)
         finally:
             # the engine is cached per device (get_engine): a failed step must not leave later
@@ -822,6 +875,9 @@ class LocalJob:
             for o, it in zip(runner.outs, items):
                 for f in tl_fields:
                     host[f][:, it.tile.p0:it.tile.p1] = o[f][:, :it.tile.n].numpy()
+            if vt is not None:
+                for k in range(len(items)):
+                    vertices(k)
         for a in host.values():
             if isinstance(a, np.memmap):
                 a.flush()
@@ -884,6 +940,9 @@ class LocalJob:
             idx = torch.from_numpy(bad).to(self.dev_planes['matched'].device)
             self.dev_planes['matched'][:, idx] = 0
             self.host_trendline['winner'][:, bad] = -1  # no trendline key either
+            if self.vertex_planes is not None:  # nor a vertex
+                self.vertex_planes['n_vertices'][idx.to(
+                    self.vertex_planes['n_vertices'].device)] = 0
             self._host = None
 
     # 4. output_reducer
@@ -896,7 +955,8 @@ class LocalJob:
         import torch
         from .raster import (FTV_ATTRS, _np_dtype, _strip_rows, device_encodable, label_rasters,
                              label_rasters_device, output_reducer, raster_path,
-                             trendline_rasters, trendline_rasters_device, write_tiff_strips)
+                             trendline_rasters, trendline_rasters_device, vertex_rasters,
+                             vertex_rasters_device, write_tiff_strips)
         tmpl = GeoTiff(self.rast_fns[0])
         rows, cols = tmpl.height, tmpl.width
         lng, lat = self.grid_xy
@@ -1002,6 +1062,9 @@ class LocalJob:
                                                  tdt, self.raster_mode,
                                                  device_sink=dsink).items():
                     write(k, a)
+                if self.vertex_planes is not None:
+                    vertex_rasters_device(self.engine, self.vertex_planes, (rows, cols), ddest,
+                                          tdt, self.raster_mode, sink=write, device_sink=dsink)
                 if self.trendline:
                     rows_dev = _DeviceRows(self.host_trendline, dp['status'].device)
                     trendline_rasters_device(self.engine, rows_dev, self.scene, self.scene.dates,
@@ -1014,6 +1077,11 @@ class LocalJob:
                             self.scene, self.scene.dates, (rows, cols), ddest, tdt,
                             self.raster_mode, attrs=FTV_ATTRS, sink=write, device_sink=dsink,
                             prefix='ftv/%s/' % name)
+                        if self._ftv_vertex is not None:
+                            vertex_rasters_device(self.engine, self._ftv_vertex, (rows, cols),
+                                                  ddest, tdt, self.raster_mode, sink=write,
+                                                  device_sink=dsink,
+                                                  prefix='ftv/%s/vertices/' % name)
                         settle(0)  # every raster of the equation is written: its planes are free
                 settle(0)
             finally:
@@ -1029,6 +1097,18 @@ class LocalJob:
             b[..., dest] = a  # repeated offsets: the last grid point wins, as in the loop
             placed[k] = b
         rasters = label_rasters(placed, self.rules, (rows, cols), tdt, self.raster_mode)
+
+        def place_table(table):  # a vertex table's planes in raster order (no vertex elsewhere)
+            res = {}
+            for k, t in table.items():
+                a = t.cpu().numpy()
+                b = np.zeros(a.shape[:-1] + (n,), a.dtype)
+                b[..., dest] = a
+                res[k] = b
+            return res
+        if self.vertex_planes is not None:
+            rasters.update(vertex_rasters(place_table(self.vertex_planes), (rows, cols), tdt,
+                                          self.raster_mode))
         if self.trendline:
             rasters.update(trendline_rasters(placed, self.scene, self.scene.dates, (rows, cols),
                                              tdt, self.raster_mode))
@@ -1044,6 +1124,11 @@ class LocalJob:
                     trendline_rasters(fplaced, self.scene, self.scene.dates, (rows, cols), tdt,
                                       self.raster_mode, attrs=FTV_ATTRS, prefix='ftv/%s/' % name),
                     tmpl, self.root, self.job))
+                if self._ftv_vertex is not None:
+                    res.update(output_reducer(
+                        vertex_rasters(place_table(self._ftv_vertex), (rows, cols), tdt,
+                                       self.raster_mode, prefix='ftv/%s/vertices/' % name),
+                        tmpl, self.root, self.job))
         self.encode_stats = {'device': 0, 'host': len(res)}
         self._join_grid()
         return res
@@ -1056,7 +1141,11 @@ class LocalJob:
         six planes come down — so the device never holds more than one tile of FTV planes. The
         host planes are reused by the next equation: the caller is done with them before it asks
         for the next. A pixel the analysis rejected has no winner there (_check_errors), so it gets
-        no FTV raster either."""
+        no FTV raster either. With settings.json vertex_table, self._ftv_vertex holds the
+        equation's vertex table while the caller has its planes (its val_fit / val_raw at the
+        analysis's vertices, compacted per tile like the analysis's own; device planes [V, P],
+        dropped before the next equation's are made), else None."""
+        self._ftv_vertex = None
         eqns = self.settings.get('ftv_eqns') or {}
         if not eqns:
             return
@@ -1074,8 +1163,20 @@ class LocalJob:
         host = {f: np.empty((Y, P), np.float64) for f in FTV_FIELDS}
         nmax = max([t.n for t in self.mosaic.mine] + [1])
         buf = torch.empty((len(FTV_FIELDS), Y, nmax), dtype=torch.float64, device=dev)
+        from .settings import vertex_cap
+        V = vertex_cap(self.settings, Y)
+        if V is not None:  # the flags in rows of the FTV planes' stride (Engine.vertex_table)
+            wbuf = torch.empty((Y, nmax), dtype=torch.int16, device=dev)
+            xbuf = torch.empty((Y, nmax), dtype=torch.uint8, device=dev)
         for name, eqn in eqns.items():
             t0 = time.perf_counter()
+            self._ftv_vertex = vt = None
+            if V is not None:
+                vt = self._ftv_vertex = {
+                    'n_vertices': torch.empty(P, dtype=torch.int32, device=dev),
+                    'vertex_year': torch.empty((V, P), dtype=torch.int32, device=dev),
+                    'vertex_fit': torch.empty((V, P), dtype=torch.float64, device=dev),
+                    'vertex_raw': torch.empty((V, P), dtype=torch.float64, device=dev)}
             prog = IndexProgram(eqn, band_dtype=b_dtype, raster_count=max(numbers))
             slots = [numbers.index(b) for b in prog.bands]  # the planes the equation reads
             fn = eng.compile_index(prog)
@@ -1086,10 +1187,17 @@ class LocalJob:
                 bands = torch.from_numpy(np.ascontiguousarray(t_bands[:, slots])).to(dev)
                 out = {f: buf[i, :, :t.n] for i, f in enumerate(FTV_FIELDS)}
                 eng.ftv_tile(self.scene, *flags, eng.index_tile(fn, bands), out=out)
+                if vt is not None:
+                    wbuf[:, :t.n].copy_(flags[0])
+                    xbuf[:, :t.n].copy_(flags[2])
+                    eng.vertex_table(self.scene.years, out['val_fit'], xbuf[:, :t.n],
+                                     winner=wbuf[:, :t.n], val_raw=out['val_raw'], max_vertices=V,
+                                     out={f: a[..., t.p0:t.p1] for f, a in vt.items()})
                 for f, o in out.items():
                     host[f][:, t.p0:t.p1] = o.cpu().numpy()
             self.ftv_s[name] = time.perf_counter() - t0
             yield name, host
+        self._ftv_vertex = None
 
     def run(self):
         """Every rank runs setup/parse/analysis; the writer (rank 0) also writes the rasters.

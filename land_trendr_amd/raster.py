@@ -123,6 +123,45 @@ def trendline_rasters(out, scene, dates, shape, template_dtype=np.int16, mode='r
     return res
 
 
+# the vertex table's rasters ('vertices/<kk>-<attr>'): attribute -> (table plane, typed type)
+VERTEX_ATTRS = (('year', 'vertex_year', np.int32), ('val_fit', 'vertex_fit', np.float64),
+                ('val_raw', 'vertex_raw', np.float64))
+
+
+def vertex_rasters(table, shape, template_dtype=np.int16, mode='reference', prefix='vertices/'):
+    """A vertex table (Engine.vertex_table's planes, host or device, P = rows * cols of `shape`)
+    -> {'vertices/n_vertices', 'vertices/<kk>-year', '<kk>-val_fit', '<kk>-val_raw'}, kk = 01 ..
+    the largest count among the pixels (at most the table's V rows). A pixel with fewer than two
+    vertices has no segment and emits nothing, not even n_vertices; pixel p carries vertex kk when
+    n_vertices[p] >= kk, all others NODATA. Values as label_rasters converts them ('typed':
+    int32 counts and years, float64 values). Planes the table lacks (vertex_raw) are left out;
+    prefix: the keys' first part (a fit-to-vertex equation's: 'ftv/<name>/vertices/')."""
+    rows, cols = shape
+    n = rows * cols
+    nv = _np(table['n_vertices'])[:n].astype(np.int64)
+    nv = np.where(nv >= 2, nv, 0)
+    res = {}
+    if not nv.any():
+        return res
+    V = _np(table['vertex_year']).shape[0]
+
+    def conv(plane, sel, typ):
+        plane, sel = plane.reshape(rows, cols), sel.reshape(rows, cols)
+        if mode == 'typed':
+            return np.where(sel, plane, NODATA).astype(typ)
+        hdt = holder_dtype(template_dtype)
+        holder = np.full((rows, cols), NODATA, hdt)
+        holder[sel] = _holder_cast(plane[sel], hdt)
+        return gdal_to_byte(holder)
+
+    res[prefix + 'n_vertices'] = conv(nv, nv > 0, np.int32)
+    for j in range(min(int(nv.max()), V)):
+        for a, f, typ in VERTEX_ATTRS:
+            if f in table:
+                res['%s%02d-%s' % (prefix, j + 1, a)] = conv(_np(table[f])[j, :n], nv > j, typ)
+    return res
+
+
 def _np(t):
     try:
         import torch
@@ -493,6 +532,51 @@ def trendline_rasters_device(engine, planes, scene, dates, shape, dest=None,
                 j.fill = 0.0
             jobs.append(j)
             outs.append(('%s%s-%s' % (prefix, names[o], a), out))
+        engine.raster_assemble(jobs)
+        if device_sink is not None:
+            device_sink([(key, out.view(rows, cols)) for key, out in outs])
+            continue
+        for key, out in outs:
+            arr = out.cpu().numpy().reshape(rows, cols)
+            if sink is not None:
+                sink(key, arr)
+            else:
+                res[key] = arr
+    return res
+
+
+def vertex_rasters_device(engine, table, shape, dest=None, template_dtype=np.int16,
+                          mode='reference', sink=None, device_sink=None, prefix='vertices/'):
+    """vertex_rasters for a table in device memory: the selector (n_vertices >= kk, and >= 2) is
+    made on the device, each raster assembled by lt_raster_assemble (LT_SEL_NONZERO), one vertex's
+    rasters at a time; sink / device_sink as trendline_rasters_device. One small copy to the host
+    first: the largest count, which decides how many vertices get rasters."""
+    import torch
+    from .index_eqn import DTYPES
+    rows, cols = shape
+    n_out = rows * cols
+    nv = table['n_vertices']
+    P = nv.shape[0]
+    top = min(int(nv.max()) if P else 0, table['vertex_year'].shape[0])
+    res = {}
+    if top < 2:
+        return res
+    ref = mode == 'reference'
+    hdt = DTYPES[holder_dtype(template_dtype)] if ref else 0
+    lt_t = {torch.uint8: _abi.LT_T_U8, torch.int32: _abi.LT_T_I32, torch.float64: _abi.LT_T_F64}
+    for j in range(top):
+        sel = (nv > max(j, 1)).to(torch.uint8)
+        batch = [('n_vertices', nv, np.int32)] if j == 0 else []
+        batch += [('%02d-%s' % (j + 1, a), table[f][j], typ) for a, f, typ in VERTEX_ATTRS
+                  if f in table]
+        jobs, outs = [], []
+        for key, plane, typ in batch:
+            tt = torch.uint8 if ref else (torch.float64 if typ == np.float64 else torch.int32)
+            out = torch.empty(n_out, dtype=tt, device=engine.device)
+            jobs.append(_job(P, n_out, plane, _abi.LT_SEL_NONZERO, sel, 0, hdt, 0.0, dest,
+                             _abi.LT_RASTER_REFERENCE if ref else _abi.LT_RASTER_TYPED, lt_t[tt],
+                             out))
+            outs.append((prefix + key, out))
         engine.raster_assemble(jobs)
         if device_sink is not None:
             device_sink([(key, out.view(rows, cols)) for key, out in outs])

@@ -54,12 +54,38 @@ def check_ftv_eqns(settings):
     return settings
 
 
+def check_vertex_table(settings):
+    """settings['vertex_table'], if present: true (a vertex table with as many vertex slots as the
+    scene has years) or an integer cap on the slots in [2, LT_MAX_YEARS]. Anything else (false,
+    a float, a string, a cap outside the range) is a ValueError; an absent key changes nothing."""
+    if 'vertex_table' not in settings:
+        return settings
+    v = settings['vertex_table']
+    if v is True:
+        return settings
+    if isinstance(v, bool) or not isinstance(v, int) or not 2 <= v <= _abi.LT_MAX_YEARS:
+        raise ValueError('vertex_table must be true or an integer in [2, %d], not %r'
+                         % (_abi.LT_MAX_YEARS, v))
+    return settings
+
+
+def vertex_cap(settings, n_years):
+    """The vertex slots V of a scene with n_years year slots under settings['vertex_table'] (a
+    pixel has at most n_years vertices, so a larger cap adds nothing), or None if the key is
+    absent."""
+    if 'vertex_table' not in check_vertex_table(settings):
+        return None
+    v = settings['vertex_table']
+    return max(n_years, 1) if v is True else min(v, max(n_years, 1))
+
+
 def load_settings(path_or_dict):
     """Read a settings.json (path, JSON text or dict) the way get_settings does (utils.py:241).
-    The one key the reference does not have, ftv_eqns, is validated here (check_ftv_eqns)."""
+    The keys the reference does not have, ftv_eqns and vertex_table, are validated here
+    (check_ftv_eqns, check_vertex_table)."""
     if isinstance(path_or_dict, dict):
-        return check_ftv_eqns(path_or_dict)
+        return check_vertex_table(check_ftv_eqns(path_or_dict))
     if path_or_dict.lstrip().startswith('{'):
-        return check_ftv_eqns(json.loads(path_or_dict))
+        return check_vertex_table(check_ftv_eqns(json.loads(path_or_dict)))
     with open(path_or_dict) as fh:
-        return check_ftv_eqns(json.load(fh))
+        return check_vertex_table(check_ftv_eqns(json.load(fh)))

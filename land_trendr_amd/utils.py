@@ -18,11 +18,11 @@ from . import _abi
 from .classes import Disturbance, LabelRule, Trendline, TrendlinePoint
 from .engine import ALL_FIELDS, FTV_FIELDS, LABELS, get_engine, label_tile
 from .scene import build_scene, parse_date
-from .settings import compile_params, load_settings
+from .settings import compile_params, load_settings, vertex_cap
 
 __all__ = ['parse_date', 'analyze', 'change_labeling', 'analysis_reducer',
            'analysis_reducer_batch', 'analyze_tile', 'index_tile', 'match_rules_gpu',
-           'fit_to_vertices_tile']
+           'fit_to_vertices_tile', 'vertex_table', 'disturbances_from_vertices']
 
 
 def _raise_for_status(status, n_obs_valid):
@@ -48,6 +48,41 @@ def fit_to_vertices_tile(scene, winner, spike, vertex, values, fields=FTV_FIELDS
     second index's values ([K, P]) -> that index's trendline planes at the same vertices
     (vertices2eqns + eqns2fitted_points, utils.py:646-722; see Engine.ftv_tile)."""
     return get_engine(device).ftv_tile(scene, winner, spike, vertex, values, fields, out)
+
+
+def vertex_table(years, val_fit, vertex, present=None, winner=None, val_raw=None,
+                 max_vertices=None, out=None, device=None):
+    """The vertex table on the GPU: per-year planes ([Y, P]) -> one row per vertex per pixel,
+    'n_vertices' [P] and 'vertex_year' / 'vertex_fit' / 'vertex_raw' [V, P] (see
+    Engine.vertex_table)."""
+    return get_engine(device).vertex_table(years, val_fit, vertex, present, winner, val_raw,
+                                           max_vertices, out)
+
+
+def disturbances_from_vertices(table):
+    """Trendline.parse_disturbances (classes.py:156-176) from a vertex table, in numpy on the
+    host: table holds 'n_vertices' [P], 'vertex_year' and 'vertex_fit' [V, P] (tensors or
+    arrays). Returns {'n_segments' [P] int32, 'onset_year', 'duration' [V-1, P] int32,
+    'initial_val', 'magnitude' [V-1, P] float64}: segment j of a pixel runs from vertex j to
+    vertex j + 1, onset = year[j], duration = year[j+1] - year[j], initial_val = fit[j],
+    magnitude = fit[j] - fit[j+1] (the reference's one subtraction, so its bits). Slots from
+    n_segments on hold LT_NODATA; a table capped below a pixel's count yields its first V - 1
+    segments."""
+    def arr(t):
+        return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    n = arr(table['n_vertices']).astype(np.int64)
+    year, fit = arr(table['vertex_year']), arr(table['vertex_fit'])
+    V = year.shape[0]
+    n_seg = np.clip(np.minimum(n, V) - 1, 0, None).astype(np.int32)
+    live = np.arange(V - 1)[:, None] < n_seg[None, :]
+    with np.errstate(invalid='ignore', over='ignore'):
+        mag = fit[:-1] - fit[1:]
+    nd = _abi.LT_NODATA
+    return {'n_segments': n_seg,
+            'onset_year': np.where(live, year[:-1], nd).astype(np.int32),
+            'duration': np.where(live, year[1:] - year[:-1], nd).astype(np.int32),
+            'initial_val': np.where(live, fit[:-1], float(nd)),
+            'magnitude': np.where(live, mag, float(nd))}
 
 
 def analyze(pix_datas, line_cost, target_date):
@@ -155,7 +190,13 @@ def analysis_reducer_batch(dates, values, valid, settings, fields=LABELS + ('sta
     settings['ftv_eqns'] ({name: equation}; needs bands): when the trendline planes winner,
     spike and vertex are among `fields`, every equation is evaluated on the bands as index_eqn
     would be and fitted to the analysis's vertices; out['ftv'][name][field] holds its FTV_FIELDS
-    planes and its 'status'."""
+    planes and its 'status'.
+
+    settings['vertex_table'] (true, or a cap on the vertex slots): out['vertex_table'] holds the
+    analysis's vertex table (Engine.vertex_table: n_vertices, vertex_year, vertex_fit,
+    vertex_raw), and out['ftv'][name]['vertex_table'] each equation's: its val_fit / val_raw at
+    the analysis's vertices. The planes the table is made from are analysed even if `fields`
+    does not name them; only the fields asked for are returned."""
     settings = load_settings(settings)
     scene = build_scene(dates, parse_date(settings['target_date']))
     params, rules = compile_params(settings['line_cost'], settings.get('label_rules', ()),
@@ -164,8 +205,13 @@ def analysis_reducer_batch(dates, values, valid, settings, fields=LABELS + ('sta
         if settings.get('mask_eqn'):
             valid = mask_tile(settings['mask_eqn'], bands, valid, band_numbers, device=device)
         values = index_tile(settings['index_eqn'], bands, band_numbers, device=device)
+    V = vertex_cap(settings, scene.n_years)
+    asked = tuple(fields)
+    if V is not None:
+        fields = asked + tuple(f for f in ('winner', 'val_raw', 'val_fit', 'vertex')
+                               if f not in asked)
     out = analyze_tile(scene, params, values, valid, fields, device=device)
-    if settings.get('ftv_eqns') and all(f in out for f in ('winner', 'spike', 'vertex')):
+    if settings.get('ftv_eqns') and all(f in asked for f in ('winner', 'spike', 'vertex')):
         if bands is None:
             raise ValueError('ftv_eqns needs the band planes (bands=...)')
         out['ftv'] = {
@@ -173,6 +219,17 @@ def analysis_reducer_batch(dates, values, valid, settings, fields=LABELS + ('sta
                                        index_tile(eqn, bands, band_numbers, device=device),
                                        device=device)
             for name, eqn in settings['ftv_eqns'].items()}
+    if V is not None:
+        years = scene.years
+        out['vertex_table'] = vertex_table(years, out['val_fit'], out['vertex'],
+                                           winner=out['winner'], val_raw=out['val_raw'],
+                                           max_vertices=V, device=device)
+        for f in out.get('ftv', {}).values():
+            f['vertex_table'] = vertex_table(years, f['val_fit'], out['vertex'],
+                                             winner=out['winner'], val_raw=f['val_raw'],
+                                             max_vertices=V, device=device)
+        for f in set(fields) - set(asked):
+            del out[f]
     out['_scene'] = scene
     out['_rules'] = rules
     return out

@@ -17,6 +17,12 @@ would, on cuda:0, and the script prints one JSON line:
                               [--decode {host,device}] [--encode {host,device}]
                               [--sample {host,device}] [--shift N] [--mask PROB]
                               [--mask-eqn EQN | --qa-cloudmask] [--ftv EQN]
+                              [--vertex-table [CAP]]
+
+--vertex-table [CAP] (with or without --trendline): settings.json gets vertex_table true, or the
+integer CAP, so every tile's vertices are compacted on the GPU during the analysis and the output
+step writes the 'vertices/...' rasters; the line reports their number, their bytes and the table's
+device bytes.
 
 --ftv EQN (needs --trendline): settings.json gets ftv_eqns {'ftv': EQN} (e.g. 'B1'), so the output
 step also runs the fit-to-vertex pass for that equation and writes its 'ftv/ftv/<date>-<attr>'
@@ -226,6 +232,9 @@ def main():
     ap.add_argument('--ftv', default=None,
                     help="settings.json ftv_eqns {'ftv': EQN} (e.g. 'B1'): the fit-to-vertex pass "
                          'of one equation in the output step (needs --trendline)')
+    ap.add_argument('--vertex-table', nargs='?', const='true', default=None, metavar='CAP',
+                    help="settings.json vertex_table: true, or the integer CAP on a pixel's "
+                         'vertices (the vertex table and its vertices/ rasters)')
     ap.add_argument('--reuse', action='store_true',
                     help='use the stack an earlier --keep run left in --work (written with the '
                          'same size and format options) instead of writing it again: runs that '
@@ -263,6 +272,9 @@ def main():
             if not a.trendline:
                 ap.error('--ftv needs --trendline')
             settings['ftv_eqns'] = {'ftv': a.ftv}
+        settings.pop('vertex_table', None)
+        if a.vertex_table:
+            settings['vertex_table'] = True if a.vertex_table == 'true' else int(a.vertex_table)
         with open(spath, 'w') as f:
             json.dump(settings, f)
         P = a.rows * a.cols
@@ -339,6 +351,15 @@ def main():
         if a.ftv:
             res['ftv_eqn'] = a.ftv
             res['ftv_pass_s'] = {k: round(v, 3) for k, v in j.ftv_s.items()}
+        if a.vertex_table:
+            vfiles = [p for k, v in files.items() if '/vertices/' in '/' + k for p in v]
+            vp = j.vertex_planes
+            res['vertex_table'] = {
+                'setting': settings['vertex_table'], 'max_vertices': int(vp['vertex_year'].shape[0]),
+                'vertices_max': int(vp['n_vertices'].max()),
+                'vertices_per_pixel': round(float(vp['n_vertices'].sum()) / P, 3),
+                'device_bytes': sum(t.numel() * t.element_size() for t in vp.values()),
+                'rasters': len(vfiles), 'raster_bytes': sum(os.path.getsize(p) for p in vfiles)}
         if a.diag:
             res['diag'] = diag(j)
         if a.check > 0:
