@@ -78,6 +78,13 @@
 #else
 #define LT_DP_TRIPLE_SPEC 0
 #endif
+// the lazy DP's trackers seeded from the 1- and 2-point starts (lt_pixel.h LT_DP_SEED), where the
+// triple is priced directly: the same kernels again
+#if LT_DP_SEED && LT_DP_TRIPLE_SPEC
+#define LT_DP_SEED_SPEC 1
+#else
+#define LT_DP_SEED_SPEC 0
+#endif
 
 namespace lt {
 
@@ -953,6 +960,9 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
     // register window alone (lt_pixel.h dp_triple_sse); the running sums are built only when the
     // wave goes on to a second start. The same kernels as NB
     constexpr bool TRI = LT_DP_TRIPLE_SPEC != 0 && RMAX == 1;
+    // the group's best assigned to the trackers after the 1- and 2-point starts, ahead of the
+    // starts of >= 3 points (lt_pixel.h dp_lazy, SEED). The same kernels as TRI
+    constexpr bool SEED = LT_DP_SEED_SPEC != 0 && TRI;
     // TRI: the last column's gap and value difference (x_j - x_{j-1}, y_j - y_{j-1}) kept for the
     // next column's triple, where they are d2 and b (three registers, no spill)
     int pd = 0;
@@ -977,7 +987,8 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
       // interval candidates: smallest upper end (Hi: start i1, value v1, tag n1 of OPTa[j+1] if it
       // wins) and the two smallest lower ends (L1 at start iL, L2); Ve/ie: the exact candidates;
       // gv/gi/gt: the best zero-residual start on an inexact OPTa of the group's base (its
-      // interval enters the trackers at the end of the column)
+      // interval enters the trackers at the end of the column; SEED: right after the 1- and
+      // 2-point starts, which assign every tracker below, so none of these values is read)
       double Ve = inf, Hi = inf, L1 = inf, L2 = inf, v1 = inf, gv = inf;
       // U = min(Hi, Ve, gh), kept as each of them changes (each only decreases): the column's
       // current upper bound without recomputing it per start
@@ -1014,11 +1025,31 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
         const double w = __builtin_fma(0x1p-50, __builtin_fabs(v), Emax);
         const int ord = (!zok || tg < 0) ? 0 : gi < 0 ? 1 : tag_order(tg, gt, v, c);
         if (ord > 0) {  // the group's new best: the smaller start, value <= the old best
-          gi = i;
-          gt = tg;
-          gv = v;
-          gh = v + w;
-          U = __builtin_fmin(U, gh);
+          if constexpr (SEED) {
+            // The group's old best is in the trackers already (seeded below, or entered here);
+            // the new one replaces it. Same base and a tag no larger: its value is <= the old
+            // one's, and so are its half-width (Emax is the column's) and both ends of its
+            // interval. track() is right for Hi, a minimum the old end cannot hold against the
+            // new one, and for L1 / L2 unless the old entry holds L1 (iL == gi; also when nothing
+            // is tracked yet, iL == gi == -1, where it changes nothing): then L2 is the smallest
+            // lower end of all other starts and must stay, where track would demote the old
+            // entry into it as if the group had two members (every such column ambiguous:
+            // L2 <= H). With it the trackers are what entering only the final best gives
+            // (lt_pixel.h dp_lazy has the cases).
+            const bool own = iL == gi;
+            const double l2 = L2;
+            gi = i;
+            gt = tg;
+            gv = v;
+            track(i, v, v + w, v - w, tg + 1);
+            L2 = own ? l2 : L2;
+          } else {
+            gi = i;
+            gt = tg;
+            gv = v;
+            gh = v + w;
+            U = __builtin_fmin(U, gh);
+          }
         } else if (ord == 0) {
           track(i, v, v + w, v - w, tg < 0 ? -1 : tg + 1);
         }  // ord < 0: strictly above the group's best, never the first minimum
@@ -1042,6 +1073,24 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
         gi = pick1 ? j - 1 : (g0 ? j : -1);
         gt = pick1 ? tg_jm1 : tg_j;
         gv = pick1 ? v1s : (g0 ? v0 : inf);
+        if constexpr (SEED) {
+          // The trackers start as the group's interval: what track() would leave in trackers of
+          // +inf, assigned. An empty group has gv = +inf: w and Hi are +inf, gv - w is NaN and the
+          // minimum with +inf returns +inf, so nothing is decided by it (i1 = iL = -1 until a
+          // start is tracked). Entering the group ahead of the starts of >= 3 points instead of
+          // after them changes no decision: Hi, L1 and L2 are minima, free of the order of
+          // entry; on equal upper or lower ends i1 / iL may name the other start, but then two
+          // lower ends are <= H or Ve decides, and the column is certain or ambiguous either
+          // way; in every certain or one-candidate column a, vnew, tnew and enew are the same
+          // bits. (U needs no gh: Hi <= the group's upper end from here on)
+          const double w = __builtin_fma(0x1p-50, __builtin_fabs(gv), Emax);
+          Hi = gv + w;
+          v1 = gv;
+          i1 = iL = gi;
+          n1 = gt + 1;
+          L1 = __builtin_fmin(gv - w, inf);
+          L2 = inf;
+        } else
         gh = gv + __builtin_fma(0x1p-50, __builtin_fabs(gv), Emax);
         const bool left = g0 && g1 && ord == 0;  // start j-1 beside the group's start j
         if (__ballot(left)) {
@@ -1051,7 +1100,8 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
           }
         }
       }
-      U = __builtin_fmin(__builtin_fmin(Hi, Ve), gh);
+      if constexpr (SEED) U = __builtin_fmin(Hi, Ve);
+      else U = __builtin_fmin(__builtin_fmin(Hi, Ve), gh);
       // prefix bound for the early exit below: every segment ending at j has Syy <= SyyAll
       wx0 = L.xn[j][lane];
       wy0 = (double)L.ys[j][lane];
@@ -1278,8 +1328,9 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
           }
         }
       }
-      // the group's best enters the trackers (an empty group: gv = inf, no effect)
-      {
+      // the group's best enters the trackers (an empty group: gv = inf, no effect); SEED: it is
+      // there since the 1- and 2-point starts
+      if constexpr (!SEED) {
         const double w = __builtin_fma(0x1p-50, __builtin_fabs(gv), Emax);
         track(gi, gv, gv + w, gv - w, gt + 1);
       }

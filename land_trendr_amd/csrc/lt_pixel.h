@@ -440,6 +440,16 @@ __host__ __device__ inline double dp_start_bound_nb(double e, double opta, doubl
 #ifndef LT_DP_TRIPLE
 #define LT_DP_TRIPLE 1
 #endif
+// The lazy DP's interval trackers seeded from the column's 1- and 2-point starts (LT_DP_SEED,
+// default on; 0 enters the group's best at the end of the column, after every other start). The
+// best inexact start among j and j-1, the group (dp_lazy below), is known before any start of >= 3
+// points is priced, so the trackers are assigned from it instead of being set to +inf and merged
+// with it after the last start; a zero-residual start of >= 3 points that becomes the group's new
+// best replaces the group's entry in the trackers. The kernels: lt_fast.h column, where the
+// switch takes effect in the modules that price the first triple directly (LT_DP_TRIPLE_SPEC).
+#ifndef LT_DP_SEED
+#define LT_DP_SEED 1
+#endif
 // (from the two gaps and the two value differences a = y_j - y_{j-1}, b = y_{j-1} - y_{j-2})
 __host__ __device__ inline double dp_triple_sse_diff(int d1, int d2, double a, double b,
                                                      double& n) {
@@ -597,7 +607,38 @@ __host__ __device__ inline void dp_screened(int n, const uint8_t* xs, const doub
 // width of the uncertainty forward, and the DP goes on. Only the backtracked path matters for
 // the result: if it crosses no ambiguous column, every vertex is exact; otherwise the function
 // returns false and the pixel is re-run with dp_screened (exact OPT) by the resolve kernel.
-template <int MAXY>
+//
+// SEED (LT_DP_SEED): the group's best enters the trackers as soon as the 1- and 2-point starts j
+// and j-1 have been seen, ahead of the starts of >= 3 points, not after them.
+// - Seeding. Nothing has been tracked by then (with c > 0 both starts are zero-residual starts:
+//   exact ones go to Ve, inexact ones to the group, and only start j-1 beside a group start j of
+//   another base is tracked, which the seeded order does after the seed). Entering the group into
+//   empty trackers is an assignment: Hi = gv + gw (its start, value, width and tag with it), Li1 =
+//   gv - gw with iL1 = gi, Li2 = +inf.
+// - Replacement. A zero-residual start i of >= 3 points that tag_order puts at or below the
+//   group's best (same base, tag no larger) becomes the new best: g is non-decreasing, so its
+//   value is <= the old best's, and its half-width E + 2^-50 |v| too (0 <= v; E here is a function
+//   of the tag that grows along a base's chain, each link adding 2^-50 |v|, and in lt_fast.h it
+//   is the one bound Emax of the column), hence both ends of its interval are <= the old entry's
+//   (rounding is monotone). It is entered with track(), which is right for Hi (a
+//   minimum: the old end is >= the new one, so min over the others and the new entry is what
+//   track leaves) and for the lower ends whenever the old entry does not hold Li1: then Li2 is
+//   either the old entry's end (every other end but Li1 is >= it >= the new end, so min(new, Li2)
+//   = new is the second smallest without the old entry, and if new <= Li1 the former Li1 is) or an
+//   end of another start that is <= the old entry's (the old entry is in neither tracker, and
+//   track sees what it would see without it). When the old entry holds Li1 (iL1 == gi), Li2 is
+//   the smallest end of all the others; the new end is <= Li1, so it takes Li1 over, and Li2 must
+//   stay: track would demote the old entry into Li2, as if the group had two members, and every
+//   such column would turn ambiguous (Li2 <= H). The new entry replaces its own predecessor.
+//   With that Hi, its start, value, width and tag, Li1, Li2 and iL1 are what entering only the
+//   final best would give.
+// - Order. Hi, Li1 and Li2 are minima, independent of the order of entry. Where two starts have
+//   the same upper end, iHi may name the other one than in the unseeded order, and where two have
+//   the same lower end, iL1 may; in both cases two lower ends are <= H (or Ve decides), the column
+//   is certain or ambiguous in either order, and only an ambiguous column's carried value can
+//   differ. In every certain or one-candidate column the argmin, OPTa, E and the tag are the
+//   same bits.
+template <int MAXY, bool SEED = (LT_DP_SEED != 0)>
 __host__ __device__ inline bool dp_lazy(int n, const uint8_t* xs, const double* ys, double c,
                                         uint8_t* arg, uint64_t* amb_out = nullptr) {
   double OPTa[MAXY + 1], E[MAXY + 1];
@@ -629,6 +670,11 @@ __host__ __device__ inline bool dp_lazy(int n, const uint8_t* xs, const double* 
     int ie = -1, iHi = -1, ibest = -1, iL1 = -2, tHi = -1;
     double gv = 0.0, gw = 0.0;
     int gi = -1, gtag = 0;
+    // SEED: whether the group has entered the trackers; start j-1 beside a group start j of
+    // another base (value, width, tag), tracked after the seed
+    bool seeded = false, left = false;
+    double lv = 0.0, lw = 0.0;
+    int ltag = 0;
     auto track = [&](int i, double v, double w, int ntag) {
       const double lo = v - w, hi = v + w;
       if (hi <= Hi) {
@@ -692,17 +738,42 @@ __host__ __device__ inline bool dp_lazy(int n, const uint8_t* xs, const double* 
         const double w = E[i] + 0x1p-50 * __builtin_fabs(v);
         const int ord = gi < 0 ? 1 : tag_order(TG[i], gtag, v, c);
         if (ord > 0) {  // the group's new best (i descends: the smaller start, value <=)
+          // SEED: it replaces the group's entry (above): Li2 stays when that entry holds Li1
+          const bool own = iL1 == gi;
+          const double l2 = Li2;
           gi = i;
           gtag = TG[i];
           gv = v;
           gw = w;
+          if (SEED && seeded) {
+            track(i, v, w, TG[i] + 1);
+            if (own) Li2 = l2;
+          }
         } else if (ord < 0) {
           tracked = false;  // strictly above the group's best: never the first minimum
+        } else if (SEED && !seeded) {
+          left = true;
+          lv = v;
+          lw = w;
+          ltag = TG[i] + 1;
         } else {
           track(i, v, w, TG[i] + 1);
         }
       } else {
         track(i, v, E[i] + ws + 0x1p-50 * __builtin_fabs(v), -1);
+      }
+      if (SEED && !seeded && i == (j >= 1 ? j - 1 : j)) {  // the 1- and 2-point starts are in
+        seeded = true;
+        if (gi >= 0) {
+          Hi = gv + gw;
+          iHi = iL1 = gi;
+          vHi = gv;
+          wHi = gw;
+          tHi = gtag + 1;
+          Li1 = gv - gw;
+          Li2 = inf;
+        }
+        if (left) track(i, lv, lw, ltag);
       }
       if (tracked && v <= vbest) {  // i descends: "<=" keeps the smaller start on equal values
         vbest = v;
@@ -722,7 +793,7 @@ __host__ __device__ inline bool dp_lazy(int n, const uint8_t* xs, const double* 
     }
     E1b = E1a;
     E1a = e1;
-    if (gi >= 0) track(gi, gv, gw, gtag + 1);
+    if (!SEED && gi >= 0) track(gi, gv, gw, gtag + 1);
     const double H = Hi < Ve ? Hi : Ve;  // the exact minimum lies in [min lower bound, H]
     if (Li1 > H) {  // no interval reaches H: the exact candidates decide, bit-exactly
       arg[j] = (uint8_t)ie;
