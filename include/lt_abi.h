@@ -435,6 +435,44 @@ typedef struct {
  * LT_OK at once for n_pix == 0. */
 int lt_vertex_table(lt_ctx* ctx, const lt_vertex_in* in, const lt_vertex_out* out, void* stream);
 
+/* ---- MMU sieve (an added export of ABI 8) -----------------------------------------------------------
+ * The minimum mapping unit of a change map: one rule's label plane over a rows x cols raster
+ * (P = rows * cols, row-major: pixel q is row q / cols, column q % cols) grouped into patches, and
+ * the patches below min_pixels dropped. A patch is a maximal set of pixels with matched != 0 and
+ * one key, connected by 4- or 8-neighbourhood in the raster (the end of one row and the start of
+ * the next are no neighbours); with key NULL every matched pixel has the same key. Every pointer
+ * is a DEVICE pointer. */
+typedef struct {
+  int64_t rows, cols;
+  uint8_t* matched;           /* [P] read; written only with apply                           */
+  const int32_t* key;         /* [P], or NULL: one key for all (never written)               */
+  int32_t connectivity;       /* 4 or 8                                                      */
+  int32_t min_pixels;         /* >= 1: patches of fewer pixels are dropped (with apply)      */
+  int32_t apply;              /* != 0: matched[q] = 0 wherever 0 < size[q] < min_pixels      */
+  int32_t phases;             /* 0: all four launches. Else bit k (1, 2, 4, 8) runs launch  */
+                              /* k + 1 alone, for timing tools: the outputs are complete     */
+                              /* only after all four ran in order on the same buffers        */
+} lt_sieve_in;
+typedef struct {
+  int32_t* root;              /* [P] smallest raster index of the pixel's patch; -1 where    */
+                              /*     matched == 0                                            */
+  int32_t* size;              /* [P] pixel count of the pixel's patch; 0 where unmatched     */
+  void* workspace;            /* lt_sieve_workspace_bytes(rows, cols) bytes, 4-byte aligned; */
+  int64_t workspace_bytes;    /* its contents before and after the call mean nothing         */
+} lt_sieve_out;
+/* Bytes of workspace lt_sieve_labels needs for a rows x cols raster (8 per pixel: a parent word
+ * and a per-root counter; at least 8), or -1 for a negative size. Host only. */
+int64_t lt_sieve_workspace_bytes(int64_t rows, int64_t cols);
+/* Connected-component labelling by union-find (land_trendr_amd/csrc/lt_sieve.h, lt_sieve.hip):
+ * four launches on `stream`, nothing read back, no workgroup waiting for another. root, size and
+ * the applied matched are functions of the input alone (two calls agree in every element). Writes
+ * root[q] and size[q] for every q < P, matched only with apply, key never, and nothing past P.
+ * LT_OK at once for rows * cols == 0. LT_ERR_ARG, with nothing launched, for a null in / out /
+ * matched / root / size / workspace, negative rows or cols, a connectivity other than 4 or 8,
+ * min_pixels < 1, phases outside [0, 15], or workspace_bytes below lt_sieve_workspace_bytes(rows, cols); LT_ERR_LIMIT for
+ * rows * cols > LT_MAX_TILE_PIX. */
+int lt_sieve_labels(lt_ctx* ctx, const lt_sieve_in* in, const lt_sieve_out* out, void* stream);
+
 /* Output raster assembly: n_jobs rasters (lt_raster_job), asynchronous on `stream`: a fill of
  * every raster pixel with NODATA's converted value, then the selected grid points scattered in
  * (one pass when dest is NULL). Replaces data2raster's per-point loop (utils.py:429-438) and the

@@ -248,6 +248,20 @@ class LtVertexOut(ctypes.Structure):
                 ('vertex_raw', c_f64p)]
 
 
+class LtSieveIn(ctypes.Structure):
+    """lt_sieve_in: one rule's label plane over a rows x cols raster (lt_sieve_labels)."""
+    _fields_ = [('rows', ctypes.c_int64), ('cols', ctypes.c_int64), ('matched', c_u8p),
+                ('key', c_i32p), ('connectivity', ctypes.c_int32),
+                ('min_pixels', ctypes.c_int32), ('apply', ctypes.c_int32),
+                ('phases', ctypes.c_int32)]
+
+
+class LtSieveOut(ctypes.Structure):
+    """lt_sieve_out: the patch root and size planes [P] and the workspace (lt_sieve_labels)."""
+    _fields_ = [('root', c_i32p), ('size', c_i32p), ('workspace', ctypes.c_void_p),
+                ('workspace_bytes', ctypes.c_int64)]
+
+
 # the planes lt_vertex_table writes: (field, numpy dtype); n_vertices is [P], the others [V, P]
 VERTEX_FIELDS = [('n_vertices', 'int32'), ('vertex_year', 'int32'), ('vertex_fit', 'float64'),
                  ('vertex_raw', 'float64')]
@@ -272,7 +286,7 @@ EXPORTS = ['lt_abi_version', 'lt_ctx_create', 'lt_ctx_destroy', 'lt_last_error',
            'lt_jit_source', 'lt_analyze_tiles_ev', 'lt_tiff_decode_strips_dev',
            'lt_tiff_encode_strips_dev', 'lt_grid_sample_dev', 'lt_mask_codegen',
            'lt_mask_compile', 'lt_mask_apply', 'lt_tiff_decode_chunks_dev', 'lt_ftv_tile',
-           'lt_vertex_table']
+           'lt_vertex_table', 'lt_sieve_labels', 'lt_sieve_workspace_bytes']
 
 LT_JIT_SYNC, LT_JIT_ASYNC = 0, 1
 LT_JIT_SRC_SPEC, LT_JIT_SRC_SCENE, LT_JIT_SRC_FIELDS = 1, 2, 4
@@ -326,6 +340,9 @@ def load_lib(path=None):
                                 ctypes.POINTER(LtTileOut), vp]
     lib.lt_vertex_table.argtypes = [vp, ctypes.POINTER(LtVertexIn), ctypes.POINTER(LtVertexOut),
                                     vp]
+    lib.lt_sieve_labels.argtypes = [vp, ctypes.POINTER(LtSieveIn), ctypes.POINTER(LtSieveOut), vp]
+    lib.lt_sieve_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
+    lib.lt_sieve_workspace_bytes.restype = ctypes.c_int64
     lib.lt_ctx_set_timing.argtypes = [vp, ctypes.c_int]
     lib.lt_ctx_stage_ms.argtypes = [vp, c_f64p, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]
     lib.lt_ctx_last_deferred.argtypes = [vp, ctypes.POINTER(ctypes.c_int64)]

@@ -394,6 +394,75 @@ class Engine:
         self._check(rc, 'lt_vertex_table')
         return out
 
+    # --- MMU sieve: patches of a label plane below a minimum size (lt_sieve_labels) ---
+    def sieve(self, matched, key, shape, min_pixels, connectivity=8, apply=True, out=None,
+              _phases=None):
+        """Connected-component labelling of one label plane and the minimum mapping unit.
+        matched: uint8 [P] device tensor with unit stride over a shape = (rows, cols) raster
+        (P = rows * cols, row-major); key: int32 [P] likewise, or None (one key for all). A patch
+        is a maximal 4- or 8-connected set of pixels with matched != 0 and one key. Returns
+        {'root', 'size'}: int32 [P] device tensors, the smallest raster index of the pixel's patch
+        (-1 where unmatched) and its pixel count (0 where unmatched); with apply, matched is
+        cleared in place wherever 0 < size < min_pixels (a patch of exactly min_pixels stays).
+        key is never written. out: {'root', 'size'} tensors to fill instead. Runs on the current
+        stream and does not synchronise; the workspace (8 bytes a pixel) is allocated per call on
+        that stream."""
+        try:
+            rows, cols = (int(v) for v in shape)
+        except (TypeError, ValueError):
+            raise LtError('shape must be (rows, cols)')
+        if rows < 0 or cols < 0:
+            raise LtError('shape must not be negative')
+        P = rows * cols
+
+        def plane(name, t, dt):
+            if (not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != self.device or
+                    t.dim() != 1 or t.numel() != P or (P > 1 and t.stride(0) != 1)):
+                raise LtError('%s must be a %s [%d] tensor on %s with unit stride'
+                              % (name, str(dt).split('.')[-1], P, self.device))
+        plane('matched', matched, torch.uint8)
+        if key is not None:
+            plane('key', key, torch.int32)
+        for name, v in (('min_pixels', min_pixels), ('connectivity', connectivity)):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise LtError('%s must be an integer' % name)
+        if connectivity not in (4, 8):
+            raise LtError('connectivity must be 4 or 8')
+        if not 1 <= min_pixels <= 2 ** 31 - 1:
+            raise LtError('min_pixels must be in [1, 2^31 - 1]')
+        if out is None:
+            out = {f: torch.empty(P, dtype=torch.int32, device=self.device)
+                   for f in ('root', 'size')}
+        if set(out) != {'root', 'size'}:
+            raise LtError('sieve writes root and size, not %s' % ', '.join(sorted(out)))
+        for f, t in out.items():
+            plane('output ' + f, t, torch.int32)
+        if P == 0:
+            return out
+        nbytes = self.lib.lt_sieve_workspace_bytes(rows, cols)
+        if nbytes < 0:
+            raise LtError('raster of %d x %d pixels is above the limit' % (rows, cols))
+        if _phases is None:
+            work, phases = torch.empty(nbytes // 4, dtype=torch.int32, device=self.device), 0
+        else:  # tools/sieve_rate.py: (a workspace kept between calls, the launches to run)
+            work, phases = _phases
+        sin = _abi.LtSieveIn()
+        sin.rows, sin.cols = rows, cols
+        sin.matched = ctypes.cast(matched.data_ptr(), _abi.c_u8p)
+        if key is not None:
+            sin.key = ctypes.cast(key.data_ptr(), _abi.c_i32p)
+        sin.connectivity, sin.min_pixels, sin.apply = connectivity, min_pixels, int(bool(apply))
+        sin.phases = phases
+        sout = _abi.LtSieveOut()
+        sout.root = ctypes.cast(out['root'].data_ptr(), _abi.c_i32p)
+        sout.size = ctypes.cast(out['size'].data_ptr(), _abi.c_i32p)
+        sout.workspace, sout.workspace_bytes = work.data_ptr(), nbytes
+        st = torch.cuda.current_stream(self.device)
+        rc = self.lib.lt_sieve_labels(self.ctx, ctypes.byref(sin), ctypes.byref(sout),
+                                      ctypes.c_void_p(st.cuda_stream))
+        self._check(rc, 'lt_sieve_labels')
+        return out
+
     # --- load stage: index_eqn (rast_algebra, utils.py:447-484) ---
     def compile_index(self, program):
         """hiprtc-compile an index_eqn.IndexProgram for this device (cached per program). A

@@ -33,6 +33,11 @@ Steps, as the reference chains them:
                                       trendline=True or False), and 'ftv/<name>/vertices/...' for
                                       every fit-to-vertex equation.
 
+With settings.json mmu (N, or {"min_pixels": N, "connectivity": 4 | 8, "by": "onset_year" |
+"match"}) output() first sieves every rule's matches on the GPU (one rank, raster order): patches
+of fewer than N connected pixels with one onset year lose their match, so every label raster of
+the rule shows NODATA there; the trendline, vertex-table and FTV rasters stay as they are.
+
 Multi-rank jobs: rank 0 alone extracts the compressed rasters and writes the grid, then every rank
 reads them (a barrier between), so no rank sees a partial extraction or a truncated grid.
 
@@ -197,6 +202,10 @@ class LocalJob:
         # a pixel, kept there like the label planes) once analyze() has run; None without the key
         self.vertex_planes = None
         self._ftv_vertex = None  # the same for the fit-to-vertex equation output() is writing
+        # settings.json mmu: {rule name: {'matched': pixels matched before the sieve, 'removed':
+        # pixels it cleared}} once output() ran; None without the key
+        self.mmu_stats = None
+        self.mmu_s = 0.0  # seconds of the sieve pass in output(), its count read-back included
         if os.path.exists(self.settings_path):  # what the job cannot do is said at construction
             try:
                 with open(self.settings_path) as f:
@@ -206,6 +215,7 @@ class LocalJob:
             if isinstance(peek, dict):
                 self._check_ftv(peek)
                 self._check_vertex(peek)
+                self._check_mmu(peek)
 
     def _check_ftv(self, settings):
         """settings.json ftv_eqns: validated (settings.check_ftv_eqns), and supported by a job of
@@ -229,6 +239,16 @@ class LocalJob:
         if self._dist()[1] > 1:
             raise ValueError('vertex_table is supported on one rank only (world size %d): the '
                              'vertex table is not distributed' % self._dist()[1])
+
+    def _check_mmu(self, settings):
+        """settings.json mmu: validated (settings.check_mmu), and supported by a job of one rank;
+        ValueError otherwise."""
+        from .settings import check_mmu
+        if 'mmu' not in check_mmu(settings):
+            return
+        if self._dist()[1] > 1:
+            raise ValueError('mmu is supported on one rank only (world size %d): the sieve '
+                             'is not distributed' % self._dist()[1])
 
     @property
     def grid_fn(self):
@@ -313,6 +333,7 @@ class LocalJob:
             self.settings = json.load(f)
         self._check_ftv(self.settings)
         self._check_vertex(self.settings)
+        self._check_mmu(self.settings)
         return self.rast_fns
 
     def _internal_order(self):
@@ -945,6 +966,37 @@ class LocalJob:
                     self.vertex_planes['n_vertices'].device)] = 0
             self._host = None
 
+    def _sieve(self, rows, cols):
+        """settings.json mmu: each rule's matched row of the scene-wide label planes sieved in
+        place on their device (Engine.sieve; the key is the rule's onset_year row, or none with
+        by 'match'), after the EMPTY and rejected pixels' matches are cleared and before any
+        raster is assembled, so every label raster of a rule shows NODATA on a removed patch.
+        The trendline, vertex-table and FTV rasters are not touched. Needs the raster order (the
+        planes are then the rasters, pixel for pixel) and an engine with a sieve: there is no CPU
+        path."""
+        from .settings import mmu_options
+        opt = mmu_options(self.settings)
+        self.mmu_stats = None
+        if opt is None:
+            return
+        if self._raster_hw is None:
+            raise RuntimeError('mmu needs the raster order (every grid point on its own template '
+                               'pixel): the label planes of this job are in grid order')
+        if not hasattr(self.engine, 'sieve'):
+            raise RuntimeError('mmu needs the HIP engine (no CPU path exists)')
+        t0 = time.perf_counter()
+        dp = self.dev_planes
+        before = dp['matched'].ne(0).sum(dim=1)
+        for r in range(len(self.rules)):
+            self.engine.sieve(dp['matched'][r], dp['onset_year'][r] if opt['by'] == 'onset_year'
+                              else None, (rows, cols), opt['min_pixels'], opt['connectivity'])
+        after = dp['matched'].ne(0).sum(dim=1)
+        counts = zip(before.cpu().tolist(), after.cpu().tolist())  # the one read-back: 2 R counts
+        self.mmu_stats = {rule.name: {'matched': b, 'removed': b - a}
+                          for rule, (b, a) in zip(self.rules, counts)}
+        self.mmu_s = time.perf_counter() - t0
+        self._host = None
+
     # 4. output_reducer
     def output(self):
         """Every output key's raster, written as LZW GeoTIFF with the template's georeferencing.
@@ -974,6 +1026,7 @@ class LocalJob:
         empty = (dp['status'] & _abi.LT_ST_EMPTY) != 0
         dp['matched'].masked_fill_(empty[None, :], 0)
         self._host = None
+        self._sieve(rows, cols)
         names = [d.strftime('%Y-%m-%d') for d in self.scene.dates]
         cuda = torch.device(self.engine.device).type == 'cuda'
         distinct = self._raster_hw is not None or np.bincount(dest, minlength=rows * cols).max() <= 1

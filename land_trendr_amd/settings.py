@@ -79,13 +79,63 @@ def vertex_cap(settings, n_years):
     return max(n_years, 1) if v is True else min(v, max(n_years, 1))
 
 
+_MMU_KEYS = ('min_pixels', 'connectivity', 'by')
+
+
+def check_mmu(settings):
+    """settings['mmu'], if present: the minimum mapping unit of the label rasters. An integer N
+    is short for {"min_pixels": N}; the long form is {"min_pixels": N, "connectivity": 4 | 8,
+    "by": "onset_year" | "match"} with connectivity 8 and by "onset_year" when left out.
+    min_pixels is an integer in [1, 2^31 - 1] (1 changes nothing). Anything else (a bool, a float,
+    a string, an unknown sub-key, a missing min_pixels) is a ValueError; an absent key changes
+    nothing."""
+    if 'mmu' not in settings:
+        return settings
+    v = settings['mmu']
+    long_form = isinstance(v, dict)
+    if long_form:
+        unknown = sorted(set(v) - set(_MMU_KEYS), key=str)
+        if unknown:
+            raise ValueError('mmu has unknown keys %r (known: %s)' % (unknown, ', '.join(_MMU_KEYS)))
+        if 'min_pixels' not in v:
+            raise ValueError('mmu needs min_pixels')
+        n = v['min_pixels']
+    else:
+        n = v
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= 2 ** 31 - 1:
+        raise ValueError('mmu min_pixels must be an integer in [1, 2^31 - 1], not %r' % (n,))
+    if long_form:
+        c = v.get('connectivity', 8)
+        if isinstance(c, bool) or not isinstance(c, int) or c not in (4, 8):
+            raise ValueError('mmu connectivity must be 4 or 8, not %r' % (c,))
+        if v.get('by', 'onset_year') not in ('onset_year', 'match'):
+            raise ValueError('mmu by must be "onset_year" or "match", not %r' % (v['by'],))
+    return settings
+
+
+def mmu_options(settings):
+    """settings['mmu'] in full, {'min_pixels', 'connectivity', 'by'} with the defaults filled in,
+    or None if the key is absent."""
+    if 'mmu' not in check_mmu(settings):
+        return None
+    v = settings['mmu']
+    if not isinstance(v, dict):
+        v = {'min_pixels': v}
+    return {'min_pixels': v['min_pixels'], 'connectivity': v.get('connectivity', 8),
+            'by': v.get('by', 'onset_year')}
+
+
+def _check_added(settings):
+    return check_mmu(check_vertex_table(check_ftv_eqns(settings)))
+
+
 def load_settings(path_or_dict):
     """Read a settings.json (path, JSON text or dict) the way get_settings does (utils.py:241).
-    The keys the reference does not have, ftv_eqns and vertex_table, are validated here
-    (check_ftv_eqns, check_vertex_table)."""
+    The keys the reference does not have, ftv_eqns, vertex_table and mmu, are validated here
+    (check_ftv_eqns, check_vertex_table, check_mmu)."""
     if isinstance(path_or_dict, dict):
-        return check_vertex_table(check_ftv_eqns(path_or_dict))
+        return _check_added(path_or_dict)
     if path_or_dict.lstrip().startswith('{'):
-        return check_vertex_table(check_ftv_eqns(json.loads(path_or_dict)))
+        return _check_added(json.loads(path_or_dict))
     with open(path_or_dict) as fh:
-        return check_vertex_table(check_ftv_eqns(json.load(fh)))
+        return _check_added(json.load(fh))

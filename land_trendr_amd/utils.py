@@ -22,7 +22,7 @@ from .settings import compile_params, load_settings, vertex_cap
 
 __all__ = ['parse_date', 'analyze', 'change_labeling', 'analysis_reducer',
            'analysis_reducer_batch', 'analyze_tile', 'index_tile', 'match_rules_gpu',
-           'fit_to_vertices_tile', 'vertex_table', 'disturbances_from_vertices']
+           'fit_to_vertices_tile', 'vertex_table', 'disturbances_from_vertices', 'sieve_labels']
 
 
 def _raise_for_status(status, n_obs_valid):
@@ -57,6 +57,15 @@ def vertex_table(years, val_fit, vertex, present=None, winner=None, val_raw=None
     Engine.vertex_table)."""
     return get_engine(device).vertex_table(years, val_fit, vertex, present, winner, val_raw,
                                            max_vertices, out)
+
+
+def sieve_labels(matched, key, shape, min_pixels, connectivity=8, apply=True, out=None,
+                 device=None):
+    """The minimum mapping unit on the GPU: a label plane's matched pixels ([P] uint8 over a
+    shape = (rows, cols) raster) grouped into patches of one key ([P] int32, or None), 'root' and
+    'size' [P] int32 returned, the patches below min_pixels cleared in `matched` (see
+    Engine.sieve)."""
+    return get_engine(device).sieve(matched, key, shape, min_pixels, connectivity, apply, out)
 
 
 def disturbances_from_vertices(table):

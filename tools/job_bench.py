@@ -17,7 +17,11 @@ would, on cuda:0, and the script prints one JSON line:
                               [--decode {host,device}] [--encode {host,device}]
                               [--sample {host,device}] [--shift N] [--mask PROB]
                               [--mask-eqn EQN | --qa-cloudmask] [--ftv EQN]
-                              [--vertex-table [CAP]]
+                              [--vertex-table [CAP]] [--mmu N]
+
+--mmu N: settings.json gets mmu N, so the output step first sieves every rule's matches on the GPU
+(patches of fewer than N 8-connected pixels with one onset year lose their match); the line reports
+LocalJob.mmu_stats and the pass's seconds.
 
 --vertex-table [CAP] (with or without --trendline): settings.json gets vertex_table true, or the
 integer CAP, so every tile's vertices are compacted on the GPU during the analysis and the output
@@ -115,7 +119,9 @@ def make_stack(root, job, rows, cols, years, seed, mask_prob, shift=0, mask_eqn=
 
 def check_sample(j, n, seed=11):
     """A seeded sample of the job's pixels: the oracle on the job's own ingested bands vs every
-    output plane. Returns (pixels, {plane: mismatches})."""
+    output plane. Returns (pixels, {plane: mismatches}). With settings.json mmu the job's matched
+    plane is the sieved one: a match the oracle has and the job has not is then what the sieve
+    does (counted as 'sieved'), only a match the oracle has not is a mismatch."""
     from golden_io import _bits_equal
     from land_trendr_amd import _abi
     from land_trendr_amd.ingest import host_threads
@@ -150,6 +156,10 @@ def check_sample(j, n, seed=11):
             m = exp['matched'][:a.shape[0]].astype(bool)
             a, e = np.where(m, a, 0), np.where(m, e, 0)
         same = _bits_equal(a, e) if a.dtype.kind == 'f' else (a == e)
+        if k == 'matched' and getattr(j, 'mmu_stats', None) is not None:
+            sieved = (a == 0) & (e != 0)
+            j.mmu_sample_sieved = int(sieved.sum())  # reported beside the line's mmu stats
+            same = same | sieved
         mism[k] = int((~same).sum())
     return len(cols_s), mism
 
@@ -235,6 +245,9 @@ def main():
     ap.add_argument('--vertex-table', nargs='?', const='true', default=None, metavar='CAP',
                     help="settings.json vertex_table: true, or the integer CAP on a pixel's "
                          'vertices (the vertex table and its vertices/ rasters)')
+    ap.add_argument('--mmu', type=int, default=None, metavar='N',
+                    help='settings.json mmu: the minimum mapping unit of the label rasters, in '
+                         'pixels (the sieve pass of the output step)')
     ap.add_argument('--reuse', action='store_true',
                     help='use the stack an earlier --keep run left in --work (written with the '
                          'same size and format options) instead of writing it again: runs that '
@@ -275,6 +288,9 @@ def main():
         settings.pop('vertex_table', None)
         if a.vertex_table:
             settings['vertex_table'] = True if a.vertex_table == 'true' else int(a.vertex_table)
+        settings.pop('mmu', None)
+        if a.mmu is not None:
+            settings['mmu'] = a.mmu
         with open(spath, 'w') as f:
             json.dump(settings, f)
         P = a.rows * a.cols
@@ -360,10 +376,15 @@ def main():
                 'vertices_per_pixel': round(float(vp['n_vertices'].sum()) / P, 3),
                 'device_bytes': sum(t.numel() * t.element_size() for t in vp.values()),
                 'rasters': len(vfiles), 'raster_bytes': sum(os.path.getsize(p) for p in vfiles)}
+        if a.mmu is not None:
+            res['mmu'] = {'setting': settings['mmu'], 'stats': j.mmu_stats,
+                          'pass_s': round(j.mmu_s, 4)}
         if a.diag:
             res['diag'] = diag(j)
         if a.check > 0:
             n, mism = check_sample(j, a.check)
+            if a.mmu is not None:
+                res['mmu']['sieved_in_check_sample'] = j.mmu_sample_sieved
             res['check'] = {'pixels': n, 'mismatches': mism,
                             'checker': 'oracle/lt_oracle.c on the job\'s ingested bands'}
         print(json.dumps(res), flush=True)
