@@ -31,7 +31,9 @@ extern "C" {
 #endif
 
 #define LT_ABI_VERSION 8
-#define LT_MAX_YEARS 64   /* distinct calendar years per scene (T <= 40 in every config) */
+#define LT_MAX_YEARS 64   /* distinct calendar years per scene (T <= 40 in every bench config;
+                             checked up to 64 consecutive years with up to LT_MAX_RULES rules and
+                             LT_MAX_OBS observations: tests/test_gpu_wide.py, test_wide_host.py) */
 #define LT_MAX_OBS 1024   /* observations per scene (K*T) */
 #define LT_MAX_RULES 16
 #define LT_NODATA (-99)   /* settings.py:16 */
