@@ -475,6 +475,85 @@ int64_t lt_sieve_workspace_bytes(int64_t rows, int64_t cols);
  * rows * cols > LT_MAX_TILE_PIX. */
 int lt_sieve_labels(lt_ctx* ctx, const lt_sieve_in* in, const lt_sieve_out* out, void* stream);
 
+/* ---- change maps (an added export of ABI 8) ---------------------------------------------------------
+ * The map LandTrendr users publish: per pixel the one segment that is a loss (or a gain), passes
+ * the filters and wins the sort, with its attributes; several maps from one pass over the planes.
+ * A pixel's segments are those of label_pixel / Trendline.parse_disturbances (as lt_vertex_table
+ * walks the vertices). A segment with left vertex (yl, fl) and right vertex (yr, fr), f the stored
+ * val_fit:  onset_year = yl, duration = yr - yl, preval = fl, d = fl - fr (one IEEE subtraction),
+ * magnitude = fabs(d), rate = magnitude / (double)duration (one IEEE division).
+ * Every pointer but `year` is a DEVICE pointer. */
+#define LT_MAX_CHANGE_MAPS 8
+enum { LT_CM_LOSS = 0, LT_CM_GAIN = 1 };
+enum { LT_CS_GREATEST = 0, LT_CS_LEAST, LT_CS_NEWEST, LT_CS_OLDEST,
+       LT_CS_LONGEST, LT_CS_SHORTEST, LT_CS_STEEPEST, LT_CS_GENTLEST };
+typedef struct {
+  int32_t delta;              /* LT_CM_LOSS / LT_CM_GAIN                                     */
+  int32_t sort;               /* LT_CS_*                                                     */
+  int32_t index_sign;         /* +1: a loss is a fall of the index (sd = d); -1: a rise      */
+                              /* (sd = -d). Loss keeps sd > 0, gain sd < 0; d == 0, -0.0 or  */
+                              /* NaN is neither                                              */
+  int32_t year_set;           /* != 0: year_lo <= onset_year <= year_hi                      */
+  int32_t year_lo, year_hi;
+  int32_t mag_op, dur_op, pre_op; /* LT_Q_UNSET / GT / LT / GE / LE on magnitude,            */
+  int32_t _pad;                   /* (double)duration and preval against the values below    */
+  double mag_val, dur_val, pre_val;
+} lt_change_rule;
+typedef struct {
+  int64_t n_pix;
+  int64_t stride;             /* elements between the year planes (>= n_pix)                 */
+  int32_t n_years;            /* Y slots                                                     */
+  const int32_t* year;        /* [Y] HOST array: calendar year of each slot                  */
+  const double* val_fit;      /* [Y][stride]                                                 */
+  const uint8_t* vertex;      /* [Y][stride]                                                 */
+  const double* val_raw;      /* [Y][stride], or NULL (then no rmse / n_fit / dsnr)          */
+  const uint8_t* present;     /* [Y][stride], 0 = no point in this slot, or                  */
+  const int16_t* winner;      /* [Y][stride], a point iff >= 0; at most one of the two;      */
+                              /* neither: every slot holds a point                           */
+  const uint8_t* spike;       /* [Y][stride], or NULL (then no rmse / n_fit / dsnr)          */
+} lt_change_in;
+typedef struct {
+  int64_t stride;             /* elements between the map planes (>= n_pix)                  */
+  uint8_t* matched;           /* [M][stride] 1 where a segment was kept, else 0              */
+  int32_t* onset_year;        /* [M][stride] the winner's attributes; LT_NODATA (-99 /       */
+  int32_t* duration;          /*             -99.0) where matched is 0                       */
+  double* magnitude;
+  double* preval;
+  double* rate;
+  double* dsnr;               /* [M][stride] magnitude / rmse (+inf for a zero rmse;         */
+                              /*             LT_NODATA with n_fit == 0)                      */
+  double* rmse;               /* [P] the pixel's fit noise; LT_NODATA with n_fit == 0        */
+  int32_t* n_fit;             /* [P] the points it is taken over                             */
+} lt_change_out;
+/* n_maps change maps of every pixel in one pass over its years (land_trendr_amd/csrc/lt_change.h;
+ * a lane is a pixel), asynchronous on `stream`. Per map, a segment is kept iff its direction is
+ * the rule's and every filter that is set compares *true* (a NaN operand drops it); among the kept
+ * segments in year order the first is the winner and a later one replaces it only on a strict
+ * improvement of the sort's key (greatest / least: magnitude, newest / oldest: onset_year,
+ * longest / shortest: duration, steepest / gentlest: rate), so the first of equals wins.
+ * The fit noise: over the slots that hold a point and have spike == 0, in year order,
+ * r = val_raw - val_fit, acc = acc + r * r (product rounded, then the sum; no fused multiply-add),
+ * n_fit their count, rmse = sqrt(acc / (double)n_fit), correctly rounded.
+ * Writes each output only if non-NULL, every element [m < n_maps][p < n_pix] (rmse / n_fit:
+ * [p < n_pix]) exactly once and nothing else: no padding of a padded stride, no row >= n_maps. No
+ * status is read. LT_ERR_ARG, with nothing launched, for a null in / rules / out, negative sizes,
+ * n_maps outside [1, LT_MAX_CHANGE_MAPS], null val_fit / vertex / year with n_pix > 0 and
+ * n_years > 0, a stride below n_pix, both present and winner, rmse / n_fit / dsnr without both
+ * val_raw and spike, a delta, sort, op or index_sign outside its set, and year_set with
+ * year_lo > year_hi; LT_ERR_LIMIT for n_years > LT_MAX_YEARS or n_pix > LT_MAX_TILE_PIX; LT_OK at
+ * once for n_pix == 0. */
+int lt_change_maps(lt_ctx* ctx, const lt_change_in* in, int n_maps, const lt_change_rule* rules,
+                   const lt_change_out* out, void* stream);
+/* A label plane counted per key (the per-year area table of a change map, or of a label rule):
+ * counts[k] += the pixels with matched != 0 and key == key_lo + k for k < n_bins, and
+ * counts[n_bins] += the matched pixels whose key is outside the range. `counts` (DEVICE,
+ * n_bins + 1 words) is added to, so the caller zeroes it; integer sums, so the result is a
+ * function of the input alone. Asynchronous on `stream`. LT_ERR_ARG, with nothing launched, for a
+ * null matched / key / counts, a negative n_pix and n_bins outside [1, 256]; LT_ERR_LIMIT for
+ * n_pix > LT_MAX_TILE_PIX; LT_OK at once for n_pix == 0. */
+int lt_label_counts(lt_ctx* ctx, const uint8_t* matched, const int32_t* key, int64_t n_pix,
+                    int32_t key_lo, int32_t n_bins, uint64_t* counts, void* stream);
+
 /* Output raster assembly: n_jobs rasters (lt_raster_job), asynchronous on `stream`: a fill of
  * every raster pixel with NODATA's converted value, then the selected grid points scattered in
  * (one pass when dest is NULL). Replaces data2raster's per-point loop (utils.py:429-438) and the

@@ -262,6 +262,64 @@ class LtSieveOut(ctypes.Structure):
                 ('workspace_bytes', ctypes.c_int64)]
 
 
+LT_MAX_CHANGE_MAPS = 8
+LT_CM_LOSS, LT_CM_GAIN = 0, 1
+(LT_CS_GREATEST, LT_CS_LEAST, LT_CS_NEWEST, LT_CS_OLDEST, LT_CS_LONGEST, LT_CS_SHORTEST,
+ LT_CS_STEEPEST, LT_CS_GENTLEST) = range(8)
+LT_CM_DELTA = {'loss': LT_CM_LOSS, 'gain': LT_CM_GAIN}
+LT_CS_SORT = {'greatest': LT_CS_GREATEST, 'least': LT_CS_LEAST, 'newest': LT_CS_NEWEST,
+              'oldest': LT_CS_OLDEST, 'longest': LT_CS_LONGEST, 'shortest': LT_CS_SHORTEST,
+              'steepest': LT_CS_STEEPEST, 'gentlest': LT_CS_GENTLEST}
+LT_CM_OP = {'>': LT_Q_GT, '<': LT_Q_LT, '>=': LT_Q_GE, '<=': LT_Q_LE}
+
+
+class LtChangeRule(ctypes.Structure):
+    """lt_change_rule: one change map's direction, sort and filters (lt_change_maps)."""
+    _fields_ = [('delta', ctypes.c_int32), ('sort', ctypes.c_int32),
+                ('index_sign', ctypes.c_int32), ('year_set', ctypes.c_int32),
+                ('year_lo', ctypes.c_int32), ('year_hi', ctypes.c_int32),
+                ('mag_op', ctypes.c_int32), ('dur_op', ctypes.c_int32),
+                ('pre_op', ctypes.c_int32), ('_pad', ctypes.c_int32),
+                ('mag_val', ctypes.c_double), ('dur_val', ctypes.c_double),
+                ('pre_val', ctypes.c_double)]
+
+
+class LtChangeIn(ctypes.Structure):
+    """lt_change_in: a trendline's per-year planes (lt_change_maps)."""
+    _fields_ = [('n_pix', ctypes.c_int64), ('stride', ctypes.c_int64),
+                ('n_years', ctypes.c_int32), ('year', c_i32p), ('val_fit', c_f64p),
+                ('vertex', c_u8p), ('val_raw', c_f64p), ('present', c_u8p), ('winner', c_i16p),
+                ('spike', c_u8p)]
+
+
+class LtChangeOut(ctypes.Structure):
+    """lt_change_out: the map planes [M][stride] and the fit noise [P] (lt_change_maps)."""
+    _fields_ = [('stride', ctypes.c_int64), ('matched', c_u8p), ('onset_year', c_i32p),
+                ('duration', c_i32p), ('magnitude', c_f64p), ('preval', c_f64p),
+                ('rate', c_f64p), ('dsnr', c_f64p), ('rmse', c_f64p), ('n_fit', c_i32p)]
+
+
+def change_rule(opt):
+    """One map of settings.change_map_options (or a dict with the same keys, the filters
+    optional) as an LtChangeRule."""
+    r = LtChangeRule()
+    r.delta, r.sort = LT_CM_DELTA[opt['delta']], LT_CS_SORT[opt.get('sort', 'greatest')]
+    r.index_sign = opt.get('index_sign', 1)
+    if opt.get('year') is not None:
+        r.year_set, r.year_lo, r.year_hi = 1, opt['year'][0], opt['year'][1]
+    for key, f in (('mag', 'mag'), ('dur', 'dur'), ('preval', 'pre')):
+        if opt.get(key) is not None:
+            setattr(r, f + '_op', LT_CM_OP[opt[key][0]])
+            setattr(r, f + '_val', float(opt[key][1]))
+    return r
+
+
+# the planes lt_change_maps writes: per map [M, P], and per pixel [P]
+CHANGE_MAP_FIELDS = [('matched', 'uint8'), ('onset_year', 'int32'), ('duration', 'int32'),
+                     ('magnitude', 'float64'), ('preval', 'float64'), ('rate', 'float64'),
+                     ('dsnr', 'float64')]
+CHANGE_PIX_FIELDS = [('rmse', 'float64'), ('n_fit', 'int32')]
+
 # the planes lt_vertex_table writes: (field, numpy dtype); n_vertices is [P], the others [V, P]
 VERTEX_FIELDS = [('n_vertices', 'int32'), ('vertex_year', 'int32'), ('vertex_fit', 'float64'),
                  ('vertex_raw', 'float64')]
@@ -286,7 +344,8 @@ EXPORTS = ['lt_abi_version', 'lt_ctx_create', 'lt_ctx_destroy', 'lt_last_error',
            'lt_jit_source', 'lt_analyze_tiles_ev', 'lt_tiff_decode_strips_dev',
            'lt_tiff_encode_strips_dev', 'lt_grid_sample_dev', 'lt_mask_codegen',
            'lt_mask_compile', 'lt_mask_apply', 'lt_tiff_decode_chunks_dev', 'lt_ftv_tile',
-           'lt_vertex_table', 'lt_sieve_labels', 'lt_sieve_workspace_bytes']
+           'lt_vertex_table', 'lt_sieve_labels', 'lt_sieve_workspace_bytes', 'lt_change_maps',
+           'lt_label_counts']
 
 LT_JIT_SYNC, LT_JIT_ASYNC = 0, 1
 LT_JIT_SRC_SPEC, LT_JIT_SRC_SCENE, LT_JIT_SRC_FIELDS = 1, 2, 4
@@ -340,6 +399,10 @@ def load_lib(path=None):
                                 ctypes.POINTER(LtTileOut), vp]
     lib.lt_vertex_table.argtypes = [vp, ctypes.POINTER(LtVertexIn), ctypes.POINTER(LtVertexOut),
                                     vp]
+    lib.lt_change_maps.argtypes = [vp, ctypes.POINTER(LtChangeIn), ctypes.c_int,
+                                   ctypes.POINTER(LtChangeRule), ctypes.POINTER(LtChangeOut), vp]
+    lib.lt_label_counts.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                    vp, vp]
     lib.lt_sieve_labels.argtypes = [vp, ctypes.POINTER(LtSieveIn), ctypes.POINTER(LtSieveOut), vp]
     lib.lt_sieve_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
     lib.lt_sieve_workspace_bytes.restype = ctypes.c_int64

@@ -394,6 +394,146 @@ class Engine:
         self._check(rc, 'lt_vertex_table')
         return out
 
+    # --- change maps: loss / gain maps of a trendline (lt_change_maps, lt_change.hip) ---
+    def change_maps(self, years, rules, val_fit, vertex, present=None, winner=None, val_raw=None,
+                    spike=None, out=None, stream=None):
+        """The change maps of every pixel, all of them in one pass over its per-year planes.
+        years: the calendar year of each of the Y slots. rules: 1 to 8 maps, each a dict as
+        settings.change_map_options gives it ('delta', and optionally 'sort', 'index_sign',
+        'year', 'mag', 'dur', 'preval') or an _abi.LtChangeRule. val_fit float64 / vertex uint8:
+        [Y, P] device tensors with unit pixel stride and one shared row stride >= P; present
+        (uint8), winner (int16), val_raw (float64) and spike (uint8) likewise, each optional, at
+        most one of present / winner. Returns the dict of device tensors: 'matched' uint8,
+        'onset_year' / 'duration' int32, 'magnitude' / 'preval' / 'rate' float64, all [M, P] and
+        LT_NODATA (matched 0) where no segment was kept, and, with val_raw and spike, 'dsnr'
+        [M, P], 'rmse' [P] float64 and 'n_fit' [P] int32. out: tensors to fill instead (exactly
+        the planes to write: the [M, P] ones [>= M, >= P] sharing one row stride, 'rmse' and
+        'n_fit' [>= P]). Asynchronous on `stream`."""
+        import numpy as np
+        if (not isinstance(val_fit, torch.Tensor) or val_fit.dim() != 2 or
+                val_fit.dtype != torch.float64 or val_fit.device != self.device or
+                (val_fit.shape[1] > 1 and val_fit.stride(1) != 1)):
+            raise LtError('val_fit must be a float64 [Y, P] tensor on %s with unit pixel stride'
+                          % self.device)
+        Y, P = val_fit.shape
+        istride = val_fit.stride(0) if Y > 1 else max(P, 1)
+        if istride < P:
+            raise LtError('val_fit rows must not overlap')
+        if present is not None and winner is not None:
+            raise LtError('at most one of present / winner')
+        for name, t, dt in (('vertex', vertex, torch.uint8), ('present', present, torch.uint8),
+                            ('winner', winner, torch.int16), ('val_raw', val_raw, torch.float64),
+                            ('spike', spike, torch.uint8)):
+            if t is None and name != 'vertex':
+                continue
+            if (not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != self.device or
+                    t.shape != val_fit.shape or (P > 1 and t.stride(1) != 1) or
+                    (Y > 1 and t.stride(0) != istride)):
+                raise LtError('%s must be %s with the shape and row stride of val_fit'
+                              % (name, str(dt).split('.')[-1]))
+        yrs = np.ascontiguousarray(np.asarray(years, np.int32))
+        if yrs.ndim != 1 or len(yrs) != Y:
+            raise LtError('years must have one entry per slot')
+        if Y > _abi.LT_MAX_YEARS:
+            raise LtError('more than %d year slots' % _abi.LT_MAX_YEARS)
+        rules = list(rules)
+        M = len(rules)
+        if not 1 <= M <= _abi.LT_MAX_CHANGE_MAPS:
+            raise LtError('1 to %d change maps' % _abi.LT_MAX_CHANGE_MAPS)
+        try:
+            crules = (_abi.LtChangeRule * M)(*[
+                r if isinstance(r, _abi.LtChangeRule) else _abi.change_rule(r) for r in rules])
+        except (KeyError, TypeError, IndexError, ValueError) as e:
+            raise LtError('bad change map rule: %r' % (e,))
+        fit = val_raw is not None and spike is not None
+        map_dt = {f: _DT[d] for f, d in _abi.CHANGE_MAP_FIELDS}
+        pix_dt = {f: _DT[d] for f, d in _abi.CHANGE_PIX_FIELDS}
+        if out is None:
+            out = {f: torch.empty((M, P), dtype=dt, device=self.device)
+                   for f, dt in map_dt.items() if f != 'dsnr' or fit}
+            if fit:
+                out.update({f: torch.empty(P, dtype=dt, device=self.device)
+                            for f, dt in pix_dt.items()})
+        ostride = None
+        for f, t in out.items():
+            if f not in map_dt and f not in pix_dt:
+                raise LtError('change_maps writes %s, not %s'
+                              % (', '.join(list(map_dt) + list(pix_dt)), f))
+            if f in ('dsnr', 'rmse', 'n_fit') and not fit:
+                raise LtError('%s needs val_raw and spike' % f)
+            dt = map_dt.get(f, pix_dt.get(f))
+            if (not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != dt or
+                    t.shape[-1] < P):
+                raise LtError('output %s has wrong device/dtype/shape' % f)
+            if f in pix_dt:
+                if t.dim() != 1 or (t.numel() > 1 and t.stride(0) != 1):
+                    raise LtError('output %s must be a [P] tensor with unit stride' % f)
+                continue
+            if t.dim() != 2 or t.shape[0] < M or (t.shape[1] > 1 and t.stride(1) != 1):
+                raise LtError('output %s too small' % f)
+            s = t.stride(0) if t.shape[0] > 1 else max(P, 1)
+            if s < P:
+                raise LtError('output %s rows must not overlap' % f)
+            if ostride is None:
+                ostride = s
+            elif s != ostride:
+                raise LtError('all [M, P] outputs must share one row stride')
+        cin = _abi.LtChangeIn()
+        cin.n_pix, cin.stride, cin.n_years = P, istride, Y
+        cin.year = yrs.ctypes.data_as(_abi.c_i32p)
+        for f, t in (('val_fit', val_fit), ('vertex', vertex), ('val_raw', val_raw),
+                     ('present', present), ('winner', winner), ('spike', spike)):
+            if t is not None:
+                setattr(cin, f, ctypes.cast(t.data_ptr(), type(getattr(cin, f))))
+        cout = _abi.LtChangeOut()
+        cout.stride = ostride if ostride is not None else max(P, 1)
+        for f, t in out.items():
+            setattr(cout, f, ctypes.cast(t.data_ptr(), type(getattr(cout, f))))
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        rc = self.lib.lt_change_maps(self.ctx, ctypes.byref(cin), M, crules, ctypes.byref(cout),
+                                     ctypes.c_void_p(st.cuda_stream))
+        self._check(rc, 'lt_change_maps')
+        return out
+
+    def label_counts(self, matched, key, key_lo, n_bins, out=None):
+        """A label plane counted per key: matched uint8 [P] and key int32 [P], device tensors
+        with unit stride. Returns an int64 [n_bins + 1] device tensor: element k the pixels with
+        matched != 0 and key == key_lo + k, the last element the matched pixels whose key is
+        outside [key_lo, key_lo + n_bins). n_bins is in [1, 256]. out: an int64 [n_bins + 1]
+        tensor the counts are added to (the caller zeroes it). Runs on the current stream and
+        does not synchronise."""
+        for name, v in (('key_lo', key_lo), ('n_bins', n_bins)):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise LtError('%s must be an integer' % name)
+        if not 1 <= n_bins <= 256:
+            raise LtError('n_bins must be in [1, 256]')
+        if not -2 ** 31 <= key_lo <= 2 ** 31 - 1:
+            raise LtError('key_lo must be an int32')
+        if (not isinstance(matched, torch.Tensor) or matched.dtype != torch.uint8 or
+                matched.device != self.device or matched.dim() != 1 or
+                (matched.numel() > 1 and matched.stride(0) != 1)):
+            raise LtError('matched must be a uint8 [P] tensor on %s with unit stride'
+                          % self.device)
+        P = matched.numel()
+        if (not isinstance(key, torch.Tensor) or key.dtype != torch.int32 or
+                key.device != self.device or key.dim() != 1 or key.numel() != P or
+                (P > 1 and key.stride(0) != 1)):
+            raise LtError('key must be an int32 [%d] tensor on %s with unit stride'
+                          % (P, self.device))
+        if out is None:
+            out = torch.zeros(n_bins + 1, dtype=torch.int64, device=self.device)
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or
+                out.device != self.device or out.dim() != 1 or out.numel() != n_bins + 1 or
+                out.stride(0) != 1):
+            raise LtError('out must be an int64 [n_bins + 1] tensor on %s' % self.device)
+        if P == 0:
+            return out
+        st = torch.cuda.current_stream(self.device)
+        rc = self.lib.lt_label_counts(self.ctx, matched.data_ptr(), key.data_ptr(), P, key_lo,
+                                      n_bins, out.data_ptr(), ctypes.c_void_p(st.cuda_stream))
+        self._check(rc, 'lt_label_counts')
+        return out
+
     # --- MMU sieve: patches of a label plane below a minimum size (lt_sieve_labels) ---
     def sieve(self, matched, key, shape, min_pixels, connectivity=8, apply=True, out=None,
               _phases=None):

@@ -38,6 +38,13 @@ With settings.json mmu (N, or {"min_pixels": N, "connectivity": 4 | 8, "by": "on
 of fewer than N connected pixels with one onset year lose their match, so every label raster of
 the rule shows NODATA there; the trendline, vertex-table and FTV rasters stay as they are.
 
+With settings.json change_maps (1 to 8 maps: loss or gain, a sort, filters; settings.check_change_maps)
+each tile's change maps are evaluated on the GPU during the analysis (one rank; trendline True or
+False) into scene-wide device planes; output() clears the dropped pixels' matches, sieves each map
+that has an mmu (its own, else the top-level one), counts the pixels per onset year
+(LocalJob.change_stats) and writes 'change/<name>-onset_year', '-duration', '-magnitude', '-preval',
+'-rate', '-dsnr' for every map with a match, and 'change/rmse'.
+
 Multi-rank jobs: rank 0 alone extracts the compressed rasters and writes the grid, then every rank
 reads them (a barrier between), so no rank sees a partial extraction or a truncated grid.
 
@@ -206,6 +213,15 @@ class LocalJob:
         # pixels it cleared}} once output() ran; None without the key
         self.mmu_stats = None
         self.mmu_s = 0.0  # seconds of the sieve pass in output(), its count read-back included
+        # settings.json change_maps: the scene-wide change-map planes on the analysis's device
+        # ({'matched', 'onset_year', 'duration', 'magnitude', 'preval', 'rate', 'dsnr' [M, P],
+        # 'rmse', 'n_fit' [P]}: 41 M + 12 bytes a pixel) once analyze() has run; None without the
+        # key
+        self.change_planes = None
+        # {map name: {'matched': pixels matched before the sieve, 'removed': pixels it cleared,
+        # 'by_year': {onset year: pixels after the sieve}}} once output() ran; None without the key
+        self.change_stats = None
+        self.change_s = 0.0  # seconds of the change maps' share of analyze() and output()
         if os.path.exists(self.settings_path):  # what the job cannot do is said at construction
             try:
                 with open(self.settings_path) as f:
@@ -216,6 +232,7 @@ class LocalJob:
                 self._check_ftv(peek)
                 self._check_vertex(peek)
                 self._check_mmu(peek)
+                self._check_change_maps(peek)
 
     def _check_ftv(self, settings):
         """settings.json ftv_eqns: validated (settings.check_ftv_eqns), and supported by a job of
@@ -249,6 +266,16 @@ class LocalJob:
         if self._dist()[1] > 1:
             raise ValueError('mmu is supported on one rank only (world size %d): the sieve '
                              'is not distributed' % self._dist()[1])
+
+    def _check_change_maps(self, settings):
+        """settings.json change_maps: validated (settings.check_change_maps), and supported by a
+        job of one rank; ValueError otherwise."""
+        from .settings import check_change_maps
+        if 'change_maps' not in check_change_maps(settings):
+            return
+        if self._dist()[1] > 1:
+            raise ValueError('change_maps is supported on one rank only (world size %d): the '
+                             'change maps are not distributed' % self._dist()[1])
 
     @property
     def grid_fn(self):
@@ -334,6 +361,7 @@ class LocalJob:
         self._check_ftv(self.settings)
         self._check_vertex(self.settings)
         self._check_mmu(self.settings)
+        self._check_change_maps(self.settings)
         return self.rast_fns
 
     def _internal_order(self):
@@ -658,7 +686,7 @@ class LocalJob:
         from .index_eqn import IndexProgram, MaskProgram
         from .runner import MosaicRunner, TileInput
         from .scene import build_scene, parse_date
-        from .settings import compile_params, vertex_cap
+        from .settings import change_map_options, compile_params, vertex_cap
         st = self.stack
         P = st['n_pix']
         dist, world, rank = self._dist()
@@ -804,6 +832,32 @@ class LocalJob:
                 'vertex_fit': torch.empty((V, P), dtype=torch.float64, device=dev),
                 'vertex_raw': torch.empty((V, P), dtype=torch.float64, device=dev)}
 
+        # settings.json change_maps: likewise the tile's device planes gain what the maps are made
+        # from, and each tile's maps are evaluated (Engine.change_maps, all of them in one pass)
+        # straight into scene-wide device planes at the tile's offset
+        self._change_opts = cm_opts = change_map_options(self.settings)
+        cm_fields = tuple(f for f in ('val_fit', 'vertex', 'val_raw', 'spike')
+                          if f not in tl_fields + vt_fields) if cm_opts is not None else ()
+        self.change_planes = cm = None
+        self.change_stats = None
+        self.change_s = 0.0
+        if cm_opts is not None:
+            if not hasattr(eng, 'change_maps'):
+                raise RuntimeError('change_maps needs the HIP engine (no CPU path exists)')
+            M = len(cm_opts)
+            cm = self.change_planes = {
+                f: torch.empty((M, P), dtype=getattr(torch, d), device=dev)
+                for f, d in _abi.CHANGE_MAP_FIELDS}
+            cm.update({f: torch.empty(P, dtype=getattr(torch, d), device=dev)
+                       for f, d in _abi.CHANGE_PIX_FIELDS})
+
+        def changes(k):  # tile k's change maps, on the current stream, behind its last stage
+            t, o = items[k].tile, runner.outs[k]
+            eng.change_maps(self.scene.years, cm_opts, o['val_fit'][:, :t.n],
+                            o['vertex'][:, :t.n], winner=o['winner'][:, :t.n],
+                            val_raw=o['val_raw'][:, :t.n], spike=o['spike'][:, :t.n],
+                            out={f: a[..., t.p0:t.p1] for f, a in cm.items()})
+
         def vertices(k):  # tile k's vertices, on the current stream, behind the tile's last stage
             t, o = items[k].tile, runner.outs[k]
             eng.vertex_table(self.scene.years, o['val_fit'][:, :t.n], o['vertex'][:, :t.n],
@@ -821,7 +875,8 @@ class LocalJob:
         # 'sync' — compile first (a disk-cached module loads at once)
         jit_mode = os.environ.get('LT_JOB_JIT', 'sync' if os.environ.get('LT_JOB_JIT_SYNC') == '1'
                                   else 'off')
-        runner = MosaicRunner(eng, m, params, items, label_fields + tl_fields + vt_fields, fn,
+        runner = MosaicRunner(eng, m, params, items, label_fields + tl_fields + vt_fields + cm_fields,
+                              fn,
                               dist, exchange_fields=label_fields, ring=3 if cuda else 0,
                               jit=jit_mode != 'off')
         jit_async = cuda and runner.jit is not None and jit_mode == 'async'
@@ -862,12 +917,14 @@ class LocalJob:
             copied[k] = tls.push({f: runner.outs[k][f] for f in tl_fields}, t.n, t)
 
         # tile k-1's rows are queued behind tile k's kernels, so the copies overlap them; tile k's
-        # vertex table is queued first, behind its last stage (the step's calls are joined to the
+        # vertex table and change maps are queued first, behind its last stage (the step's calls are joined to the
         # stream at one rank) and ahead of the event that reports its ring buffer free (recorded
         # by push(k), after everything queued here)
         def after(k):
             if vt is not None:
                 vertices(k)
+            if cm is not None:
+                changes(k)
             if k > 0:
                 push(k - 1)
 
@@ -899,6 +956,11 @@ class LocalJob:
             if vt is not None:
                 for k in range(len(items)):
                     vertices(k)
+            if cm is not None:
+                t_cm = time.perf_counter()
+                for k in range(len(items)):
+                    changes(k)
+                self.change_s += time.perf_counter() - t_cm
         for a in host.values():
             if isinstance(a, np.memmap):
                 a.flush()
@@ -997,6 +1059,56 @@ class LocalJob:
         self.mmu_s = time.perf_counter() - t0
         self._host = None
 
+    def _change_output(self, rows, cols):
+        """settings.json change_maps, between the analysis and the rasters: on the planes'
+        device, `matched` is cleared on the pixels the job drops (EMPTY, and under
+        on_error='skip' the rejected ones: self._change_keep is the mask of the others), each map
+        that has an mmu above 1 is sieved in place (Engine.sieve; the key is the map's onset_year
+        row, or none with by 'match'; needs the raster order, as _sieve does), and every map is
+        counted per onset year before and after the sieve (Engine.label_counts) into
+        self.change_stats; the two [M, Y + 1] count tables are the only read-back."""
+        cm, opts = self.change_planes, self._change_opts
+        self._change_keep = None
+        if cm is None:
+            return
+        import torch
+        t0 = time.perf_counter()
+        eng = self.engine
+        for need in ('change_maps', 'label_counts'):
+            if not hasattr(eng, need):
+                raise RuntimeError('change_maps needs the HIP engine (no CPU path exists)')
+        keep = self._change_keep = (self.dev_planes['status'] == 0).to(cm['matched'].device)
+        cm['matched'].masked_fill_(~keep[None, :], 0)
+        years = [int(y) for y in self.scene.years]
+        lo = min(years)
+        n_bins = min(max(years) - lo + 1, 256)
+        M = len(opts)
+        counts = torch.zeros((2, M, n_bins + 1), dtype=torch.int64, device=cm['matched'].device)
+        for m, opt in enumerate(opts):
+            eng.label_counts(cm['matched'][m], cm['onset_year'][m], lo, n_bins, out=counts[0, m])
+            mmu = opt['mmu']
+            if mmu is not None and mmu['min_pixels'] > 1:
+                if self._raster_hw is None:
+                    raise RuntimeError('change_maps: mmu needs the raster order (every grid '
+                                       'point on its own template pixel): the planes of this '
+                                       'job are in grid order')
+                if not hasattr(eng, 'sieve'):
+                    raise RuntimeError('change_maps: mmu needs the HIP engine (no CPU path '
+                                       'exists)')
+                eng.sieve(cm['matched'][m], cm['onset_year'][m] if mmu['by'] == 'onset_year'
+                          else None, (rows, cols), mmu['min_pixels'], mmu['connectivity'])
+            eng.label_counts(cm['matched'][m], cm['onset_year'][m], lo, n_bins, out=counts[1, m])
+        c = counts.cpu().numpy()  # the one read-back
+        self.change_stats = {}
+        for m, opt in enumerate(opts):
+            before, after = int(c[0, m].sum()), int(c[1, m].sum())
+            self.change_stats[opt['name']] = {
+                'matched': before, 'removed': before - after,
+                'by_year': {y: int(c[1, m, y - lo]) for y in sorted(set(years))
+                            if y - lo < n_bins}}
+        self._change_live = [int(c[1, m].sum()) > 0 for m in range(M)]
+        self.change_s += time.perf_counter() - t0
+
     # 4. output_reducer
     def output(self):
         """Every output key's raster, written as LZW GeoTIFF with the template's georeferencing.
@@ -1007,6 +1119,7 @@ class LocalJob:
         import torch
         from .raster import (FTV_ATTRS, _np_dtype, _strip_rows, device_encodable, label_rasters,
                              label_rasters_device, output_reducer, raster_path,
+                             change_rasters, change_rasters_device,
                              trendline_rasters, trendline_rasters_device, vertex_rasters,
                              vertex_rasters_device, write_tiff_strips)
         tmpl = GeoTiff(self.rast_fns[0])
@@ -1027,6 +1140,7 @@ class LocalJob:
         dp['matched'].masked_fill_(empty[None, :], 0)
         self._host = None
         self._sieve(rows, cols)
+        self._change_output(rows, cols)
         names = [d.strftime('%Y-%m-%d') for d in self.scene.dates]
         cuda = torch.device(self.engine.device).type == 'cuda'
         distinct = self._raster_hw is not None or np.bincount(dest, minlength=rows * cols).max() <= 1
@@ -1118,6 +1232,13 @@ class LocalJob:
                 if self.vertex_planes is not None:
                     vertex_rasters_device(self.engine, self.vertex_planes, (rows, cols), ddest,
                                           tdt, self.raster_mode, sink=write, device_sink=dsink)
+                if self.change_planes is not None:
+                    t_cm = time.perf_counter()
+                    change_rasters_device(self.engine, self.change_planes, self._change_opts,
+                                          (rows, cols), ddest, tdt, self.raster_mode,
+                                          keep=self._change_keep, sink=write, device_sink=dsink,
+                                          live=self._change_live)
+                    self.change_s += time.perf_counter() - t_cm
                 if self.trendline:
                     rows_dev = _DeviceRows(self.host_trendline, dp['status'].device)
                     trendline_rasters_device(self.engine, rows_dev, self.scene, self.scene.dates,
@@ -1162,6 +1283,12 @@ class LocalJob:
         if self.vertex_planes is not None:
             rasters.update(vertex_rasters(place_table(self.vertex_planes), (rows, cols), tdt,
                                           self.raster_mode))
+        if self.change_planes is not None:
+            t_cm = time.perf_counter()
+            kept = place_table({'keep': self._change_keep})['keep']
+            rasters.update(change_rasters(place_table(self.change_planes), self._change_opts,
+                                          (rows, cols), tdt, self.raster_mode, keep=kept))
+            self.change_s += time.perf_counter() - t_cm
         if self.trendline:
             rasters.update(trendline_rasters(placed, self.scene, self.scene.dates, (rows, cols),
                                              tdt, self.raster_mode))

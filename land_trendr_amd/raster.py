@@ -162,6 +162,54 @@ def vertex_rasters(table, shape, template_dtype=np.int16, mode='reference', pref
     return res
 
 
+# a change map's rasters ('change/<name>-<attr>'): attribute (= the plane's name) -> typed type
+CHANGE_ATTRS = (('onset_year', np.int32), ('duration', np.int32), ('magnitude', np.float64),
+                ('preval', np.float64), ('rate', np.float64), ('dsnr', np.float64))
+
+
+def _map_name(m):
+    return m['name'] if isinstance(m, dict) else m
+
+
+def change_rasters(planes, maps, shape, template_dtype=np.int16, mode='reference', keep=None,
+                   prefix='change/'):
+    """Change-map planes (Engine.change_maps' output, host or device, P = rows * cols of `shape`)
+    -> {'change/<name>-onset_year', '-duration', '-magnitude', '-preval', '-rate', '-dsnr'} for
+    every map with at least one match (maps: the names, or settings.change_map_options' dicts, in
+    plane order), NODATA where the map did not match, and 'change/rmse' over the pixels with
+    n_fit > 0 (and keep[p], a [P] mask, if given) when there is one. Attributes the planes lack
+    (dsnr, rmse) are left out. Values as label_rasters converts them ('typed': int32 years and
+    durations, float64 otherwise)."""
+    rows, cols = shape
+    n = rows * cols
+    res = {}
+
+    def conv(plane, sel, typ):
+        plane, sel = plane.reshape(rows, cols), sel.reshape(rows, cols)
+        if mode == 'typed':
+            return np.where(sel, plane, NODATA).astype(typ)
+        hdt = holder_dtype(template_dtype)
+        holder = np.full((rows, cols), NODATA, hdt)
+        holder[sel] = _holder_cast(plane[sel], hdt)
+        return gdal_to_byte(holder)
+
+    matched = _np(planes['matched'])
+    for m, name in enumerate(_map_name(x) for x in maps):
+        sel = matched[m, :n] != 0
+        if not sel.any():
+            continue
+        for a, typ in CHANGE_ATTRS:
+            if a in planes:
+                res['%s%s-%s' % (prefix, name, a)] = conv(_np(planes[a])[m, :n], sel, typ)
+    if 'rmse' in planes and 'n_fit' in planes:
+        sel = _np(planes['n_fit'])[:n] > 0
+        if keep is not None:
+            sel = sel & (_np(keep)[:n] != 0)
+        if sel.any():
+            res[prefix + 'rmse'] = conv(_np(planes['rmse'])[:n], sel, np.float64)
+    return res
+
+
 def _np(t):
     try:
         import torch
@@ -571,6 +619,57 @@ def vertex_rasters_device(engine, table, shape, dest=None, template_dtype=np.int
                   if f in table]
         jobs, outs = [], []
         for key, plane, typ in batch:
+            tt = torch.uint8 if ref else (torch.float64 if typ == np.float64 else torch.int32)
+            out = torch.empty(n_out, dtype=tt, device=engine.device)
+            jobs.append(_job(P, n_out, plane, _abi.LT_SEL_NONZERO, sel, 0, hdt, 0.0, dest,
+                             _abi.LT_RASTER_REFERENCE if ref else _abi.LT_RASTER_TYPED, lt_t[tt],
+                             out))
+            outs.append((prefix + key, out))
+        engine.raster_assemble(jobs)
+        if device_sink is not None:
+            device_sink([(key, out.view(rows, cols)) for key, out in outs])
+            continue
+        for key, out in outs:
+            arr = out.cpu().numpy().reshape(rows, cols)
+            if sink is not None:
+                sink(key, arr)
+            else:
+                res[key] = arr
+    return res
+
+
+def change_rasters_device(engine, planes, maps, shape, dest=None, template_dtype=np.int16,
+                          mode='reference', keep=None, sink=None, device_sink=None,
+                          prefix='change/', live=None):
+    """change_rasters for planes in device memory: each raster assembled by lt_raster_assemble
+    (LT_SEL_NONZERO on the map's matched row; for 'change/rmse' on a selector made on the device
+    from n_fit and keep), one map's rasters at a time; sink / device_sink as
+    trendline_rasters_device. live: per map, whether it has a match at all (a map without one
+    gets no raster), if the caller knows it already; else it is one small copy to the host."""
+    import torch
+    from .index_eqn import DTYPES
+    rows, cols = shape
+    n_out = rows * cols
+    matched = planes['matched']
+    P = matched.shape[-1]
+    names = [_map_name(x) for x in maps]
+    if live is None:
+        live = matched[:len(names)].ne(0).any(dim=1).cpu().tolist()
+    ref = mode == 'reference'
+    hdt = DTYPES[holder_dtype(template_dtype)] if ref else 0
+    lt_t = {torch.uint8: _abi.LT_T_U8, torch.int32: _abi.LT_T_I32, torch.float64: _abi.LT_T_F64}
+    batches = [[('%s-%s' % (name, a), planes[a][m], matched[m], typ) for a, typ in CHANGE_ATTRS
+                if a in planes] for m, name in enumerate(names) if live[m]]
+    if 'rmse' in planes and 'n_fit' in planes:
+        sel = planes['n_fit'] > 0
+        if keep is not None:
+            sel = sel & (keep != 0)
+        if bool(sel.any()):
+            batches.append([('rmse', planes['rmse'], sel.to(torch.uint8), np.float64)])
+    res = {}
+    for batch in batches:
+        jobs, outs = [], []
+        for key, plane, sel, typ in batch:
             tt = torch.uint8 if ref else (torch.float64 if typ == np.float64 else torch.int32)
             out = torch.empty(n_out, dtype=tt, device=engine.device)
             jobs.append(_job(P, n_out, plane, _abi.LT_SEL_NONZERO, sel, 0, hdt, 0.0, dest,

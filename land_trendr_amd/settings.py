@@ -125,14 +125,117 @@ def mmu_options(settings):
             'by': v.get('by', 'onset_year')}
 
 
+CHANGE_DELTAS = ('loss', 'gain')
+CHANGE_SORTS = ('greatest', 'least', 'newest', 'oldest', 'longest', 'shortest', 'steepest',
+                'gentlest')
+CHANGE_OPS = ('>', '<', '>=', '<=')
+_CHANGE_KEYS = ('name', 'delta', 'sort', 'index_sign', 'year', 'mag', 'dur', 'preval', 'mmu')
+MAX_CHANGE_MAPS = 8  # LT_MAX_CHANGE_MAPS
+
+
+def _is_int(v):
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def _is_number(v):
+    return isinstance(v, (int, float)) and not isinstance(v, bool)
+
+
+def check_change_maps(settings):
+    """settings['change_maps'], if present: a list of 1 to 8 objects, one change map each, with
+    the keys
+      name        [A-Za-z0-9_]+, unique: the 'change/<name>-...' part of the output keys (required)
+      delta       "loss" or "gain" (required)
+      sort        "greatest" (default), "least", "newest", "oldest", "longest", "shortest",
+                  "steepest" or "gentlest": which of a pixel's kept segments the map shows
+      index_sign  1 (default: a loss is a fall of the index) or -1 (a loss is a rise)
+      year        [lo, hi], integers with lo <= hi: lo <= onset_year <= hi
+      mag, dur, preval   [op, v]: op one of ">", "<", ">=", "<=", v a number, on the segment's
+                  magnitude, duration and value before the change
+      mmu         the forms check_mmu accepts: the map's own sieve (else the top-level mmu's)
+    Anything else (an unknown key, a bool for a number, a float for a year, lo > hi, a ninth map,
+    a duplicate name, an empty list) is a ValueError that names change_maps; an absent key changes
+    nothing."""
+    if 'change_maps' not in settings:
+        return settings
+    maps = settings['change_maps']
+
+    def bad(msg):
+        return ValueError('change_maps: ' + msg)
+    if not isinstance(maps, list) or not 1 <= len(maps) <= MAX_CHANGE_MAPS:
+        raise bad('must be a list of 1 to %d objects' % MAX_CHANGE_MAPS)
+    seen = set()
+    for i, m in enumerate(maps):
+        if not isinstance(m, dict):
+            raise bad('entry %d must be an object' % i)
+        unknown = sorted(set(m) - set(_CHANGE_KEYS), key=str)
+        if unknown:
+            raise bad('entry %d has unknown keys %r (known: %s)'
+                      % (i, unknown, ', '.join(_CHANGE_KEYS)))
+        name = m.get('name')
+        if not isinstance(name, str) or not _FTV_NAME.match(name):
+            raise bad('entry %d needs a name that matches [A-Za-z0-9_]+, not %r' % (i, name))
+        if name in seen:
+            raise bad('the name %r is used twice' % name)
+        seen.add(name)
+        if m.get('delta') not in CHANGE_DELTAS or not isinstance(m.get('delta'), str):
+            raise bad('%s: delta must be "loss" or "gain", not %r' % (name, m.get('delta')))
+        s = m.get('sort', 'greatest')
+        if not isinstance(s, str) or s not in CHANGE_SORTS:
+            raise bad('%s: sort must be one of %s, not %r' % (name, ', '.join(CHANGE_SORTS), s))
+        sign = m.get('index_sign', 1)
+        if not _is_int(sign) or sign not in (1, -1):
+            raise bad('%s: index_sign must be 1 or -1, not %r' % (name, sign))
+        if 'year' in m:
+            y = m['year']
+            if (not isinstance(y, list) or len(y) != 2 or not all(_is_int(v) for v in y) or
+                    not all(-2 ** 31 <= v <= 2 ** 31 - 1 for v in y) or y[0] > y[1]):
+                raise bad('%s: year must be [lo, hi], integers with lo <= hi, not %r' % (name, y))
+        for key in ('mag', 'dur', 'preval'):
+            if key in m:
+                f = m[key]
+                if (not isinstance(f, list) or len(f) != 2 or not isinstance(f[0], str) or
+                        f[0] not in CHANGE_OPS or not _is_number(f[1])):
+                    raise bad('%s: %s must be [op, number] with op one of %s, not %r'
+                              % (name, key, ' '.join(CHANGE_OPS), f))
+        if 'mmu' in m:
+            try:
+                check_mmu({'mmu': m['mmu']})
+            except ValueError as e:
+                raise bad('%s: %s' % (name, e))
+    return settings
+
+
+def change_map_options(settings):
+    """settings['change_maps'] in full: the list of maps, each {'name', 'delta', 'sort',
+    'index_sign', 'year' ([lo, hi] or None), 'mag', 'dur', 'preval' ([op, v] or None), 'mmu'
+    (mmu_options' dict or None)} with the defaults filled in, or None if the key is absent. A
+    map's own mmu wins; without one the top-level mmu applies to the map as well; neither means
+    no sieve."""
+    if 'change_maps' not in check_change_maps(settings):
+        return None
+    top = mmu_options(settings)
+    out = []
+    for m in settings['change_maps']:
+        out.append({'name': m['name'], 'delta': m['delta'], 'sort': m.get('sort', 'greatest'),
+                    'index_sign': m.get('index_sign', 1),
+                    'year': list(m['year']) if 'year' in m else None,
+                    'mag': list(m['mag']) if 'mag' in m else None,
+                    'dur': list(m['dur']) if 'dur' in m else None,
+                    'preval': list(m['preval']) if 'preval' in m else None,
+                    'mmu': mmu_options({'mmu': m['mmu']}) if 'mmu' in m else
+                    (dict(top) if top is not None else None)})
+    return out
+
+
 def _check_added(settings):
-    return check_mmu(check_vertex_table(check_ftv_eqns(settings)))
+    return check_change_maps(check_mmu(check_vertex_table(check_ftv_eqns(settings))))
 
 
 def load_settings(path_or_dict):
     """Read a settings.json (path, JSON text or dict) the way get_settings does (utils.py:241).
-    The keys the reference does not have, ftv_eqns, vertex_table and mmu, are validated here
-    (check_ftv_eqns, check_vertex_table, check_mmu)."""
+    The keys the reference does not have, ftv_eqns, vertex_table, mmu and change_maps, are
+    validated here (check_ftv_eqns, check_vertex_table, check_mmu, check_change_maps)."""
     if isinstance(path_or_dict, dict):
         return _check_added(path_or_dict)
     if path_or_dict.lstrip().startswith('{'):

@@ -22,7 +22,8 @@ from .settings import compile_params, load_settings, vertex_cap
 
 __all__ = ['parse_date', 'analyze', 'change_labeling', 'analysis_reducer',
            'analysis_reducer_batch', 'analyze_tile', 'index_tile', 'match_rules_gpu',
-           'fit_to_vertices_tile', 'vertex_table', 'disturbances_from_vertices', 'sieve_labels']
+           'fit_to_vertices_tile', 'vertex_table', 'disturbances_from_vertices', 'sieve_labels',
+           'change_maps', 'label_counts']
 
 
 def _raise_for_status(status, n_obs_valid):
@@ -66,6 +67,37 @@ def sieve_labels(matched, key, shape, min_pixels, connectivity=8, apply=True, ou
     'size' [P] int32 returned, the patches below min_pixels cleared in `matched` (see
     Engine.sieve)."""
     return get_engine(device).sieve(matched, key, shape, min_pixels, connectivity, apply, out)
+
+
+def change_maps(years, rules, val_fit, vertex, present=None, winner=None, val_raw=None,
+                spike=None, device=None):
+    """The change maps on the GPU: per-year planes ([Y, P]) and 1 to 8 map rules -> 'matched',
+    'onset_year', 'duration', 'magnitude', 'preval', 'rate' [M, P] and, with val_raw and spike,
+    'dsnr' [M, P], 'rmse' and 'n_fit' [P] (see Engine.change_maps). numpy arrays in, numpy arrays
+    out: the planes go up, the maps come down; device tensors are taken and returned as they
+    are."""
+    eng = get_engine(device)
+    planes = (val_fit, vertex, present, winner, val_raw, spike)
+    host = not any(isinstance(t, torch.Tensor) for t in planes)
+    if host:
+        dts = (np.float64, np.uint8, np.uint8, np.int16, np.float64, np.uint8)
+        planes = [None if a is None else
+                  torch.from_numpy(np.ascontiguousarray(a, dt)).to(eng.device)
+                  for a, dt in zip(planes, dts)]
+    out = eng.change_maps(years, rules, *planes)
+    return {f: t.cpu().numpy() for f, t in out.items()} if host else out
+
+
+def label_counts(matched, key, key_lo, n_bins, device=None):
+    """A label plane counted per key on the GPU: matched [P] uint8 and key [P] int32 -> int64
+    [n_bins + 1] (see Engine.label_counts). numpy arrays in, a numpy array out; device tensors
+    are taken and returned as they are."""
+    eng = get_engine(device)
+    if isinstance(matched, torch.Tensor):
+        return eng.label_counts(matched, key, key_lo, n_bins)
+    m = torch.from_numpy(np.ascontiguousarray(matched, np.uint8).reshape(-1)).to(eng.device)
+    k = torch.from_numpy(np.ascontiguousarray(key, np.int32).reshape(-1)).to(eng.device)
+    return eng.label_counts(m, k, key_lo, n_bins).cpu().numpy()
 
 
 def disturbances_from_vertices(table):

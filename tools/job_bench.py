@@ -17,7 +17,13 @@ would, on cuda:0, and the script prints one JSON line:
                               [--decode {host,device}] [--encode {host,device}]
                               [--sample {host,device}] [--shift N] [--mask PROB]
                               [--mask-eqn EQN | --qa-cloudmask] [--ftv EQN]
-                              [--vertex-table [CAP]] [--mmu N]
+                              [--vertex-table [CAP]] [--mmu N] [--change-maps [N]]
+
+--change-maps [N]: settings.json gets change_maps with the first N (default 8) of eight maps (loss /
+gain, several sorts and filters), so every tile's change maps are made on the GPU during the
+analysis and the output step clears, sieves (with --mmu), counts and writes the 'change/...' rasters;
+the line reports LocalJob.change_stats' totals, the seconds (LocalJob.change_s), the planes' device
+bytes and the rasters' number and bytes.
 
 --mmu N: settings.json gets mmu N, so the output step first sieves every rule's matches on the GPU
 (patches of fewer than N 8-connected pixels with one onset year lose their match); the line reports
@@ -54,6 +60,20 @@ sys.path.insert(0, os.path.join(ROOT, 'tests'))
 GT = (500000.0, 30.0, 0.0, 4200000.0, 0.0, -30.0)
 SETTINGS = {'index_eqn': 'B1 - B2', 'line_cost': 10, 'target_date': '2014-07-01',
             'label_rules': [{'name': 'gd', 'val': 1, 'change_type': 'GD'}]}
+
+
+# --change-maps: loss and gain maps over the sorts and filters (the synthetic index spans about
+# -200 .. 900)
+CHANGE_MAPS = [
+    {'name': 'loss', 'delta': 'loss'},
+    {'name': 'gain_new', 'delta': 'gain', 'sort': 'newest', 'mag': ['>', 130]},
+    {'name': 'loss_steep', 'delta': 'loss', 'sort': 'steepest', 'dur': ['>', 1],
+     'preval': ['>=', 600]},
+    {'name': 'loss_big', 'delta': 'loss', 'mag': ['>', 480]},
+    {'name': 'gain_long', 'delta': 'gain', 'sort': 'longest', 'dur': ['<', 4]},
+    {'name': 'loss_90s', 'delta': 'loss', 'sort': 'oldest', 'year': [1990, 1999]},
+    {'name': 'gain_small', 'delta': 'gain', 'sort': 'least', 'mag': ['<=', 26.0]},
+    {'name': 'loss_short', 'delta': 'loss', 'sort': 'shortest', 'preval': ['<', 0]}]
 
 
 def make_stack(root, job, rows, cols, years, seed, mask_prob, shift=0, mask_eqn=None,
@@ -248,6 +268,9 @@ def main():
     ap.add_argument('--mmu', type=int, default=None, metavar='N',
                     help='settings.json mmu: the minimum mapping unit of the label rasters, in '
                          'pixels (the sieve pass of the output step)')
+    ap.add_argument('--change-maps', nargs='?', const=8, default=None, type=int, metavar='N',
+                    help='settings.json change_maps: the first N of eight maps (the change maps '
+                         "and their change/ rasters)")
     ap.add_argument('--reuse', action='store_true',
                     help='use the stack an earlier --keep run left in --work (written with the '
                          'same size and format options) instead of writing it again: runs that '
@@ -291,6 +314,11 @@ def main():
         settings.pop('mmu', None)
         if a.mmu is not None:
             settings['mmu'] = a.mmu
+        settings.pop('change_maps', None)
+        if a.change_maps is not None:
+            if not 1 <= a.change_maps <= len(CHANGE_MAPS):
+                ap.error('--change-maps takes 1 to %d' % len(CHANGE_MAPS))
+            settings['change_maps'] = CHANGE_MAPS[:a.change_maps]
         with open(spath, 'w') as f:
             json.dump(settings, f)
         P = a.rows * a.cols
@@ -379,6 +407,15 @@ def main():
         if a.mmu is not None:
             res['mmu'] = {'setting': settings['mmu'], 'stats': j.mmu_stats,
                           'pass_s': round(j.mmu_s, 4)}
+        if a.change_maps is not None:
+            cfiles = [p for k, v in files.items() if k.startswith('change/') for p in v]
+            res['change_maps'] = {
+                'maps': a.change_maps, 'pass_s': round(j.change_s, 4),
+                'stats': {k: {'matched': v['matched'], 'removed': v['removed']}
+                          for k, v in j.change_stats.items()},
+                'device_bytes': sum(t.numel() * t.element_size()
+                                    for t in j.change_planes.values()),
+                'rasters': len(cfiles), 'raster_bytes': sum(os.path.getsize(p) for p in cfiles)}
         if a.diag:
             res['diag'] = diag(j)
         if a.check > 0:
