@@ -587,10 +587,12 @@ typedef struct {
 } lt_strips_job;
 /* lt_tiff_decode_strips (lt_io.h) for n_jobs images whose compressed strips are in device memory,
  * asynchronous on `stream`; same results, same zero padding of short strips, same ignored extra
- * strips. LT_ERR_ARG for what the host function rejects and for strips of 1 MiB or more decoded.
- * One lane per strip (the LZW core of land_trendr_amd/csrc/lt_lzw_core.h, the source liblt_io.so's
- * lt_lzw_decode_core is compiled from); the context owns the lanes' string tables (16 KB a lane,
- * grown on demand). A failing strip's rows are unspecified; every other strip is decoded. */
+ * strips. LT_ERR_ARG for what the host function rejects (any compression but 1 and 5 among it:
+ * Deflate is lt_tiff_decode_chunks_dev's) and for strips of 1 MiB or more decoded.
+ * Each job is decoded as the lt_chunks_job (below) with tiled 0, chunk_w = width, chunk_h =
+ * rows_per_strip and n_chunks = n_strips, by lt_tiff_decode_chunks_dev's kernel and out of the same
+ * context scratch, with at most 256 MiB of chunk buffers (chunky strips) in flight. A failing
+ * strip's rows are unspecified; every other strip is decoded. */
 int lt_tiff_decode_strips_dev(lt_ctx* ctx, const lt_strips_job* jobs, int n_jobs, void* stream);
 
 /* ---- ingest: TIFF tiles and Deflate decoded on the device (an added export of ABI 8) -------------
@@ -624,10 +626,12 @@ typedef struct {
  * compression, predictor or planar value outside the lists above, strips whose chunk_w is not the
  * width, fewer chunks than the image has, and chunks of 1 MiB or more decoded. One lane per chunk
  * (land_trendr_amd/csrc/lt_chunk.h over lt_lzw_core.h and lt_inflate_core.h, the sources
- * liblt_io.so's lt_tiff_decode_chunks is compiled from), at most 32768 in flight; a wave's Huffman
- * tables are in LDS, the context owns the LZW string tables (16 KB a lane, LZW images only) and
- * the lanes' chunk buffers (tiles and chunky chunks; at most 1 GiB), grown on demand. A failing
- * chunk's pixels are unspecified; every other chunk is decoded. */
+ * liblt_io.so's lt_tiff_decode_chunks is compiled from), at most 32768 in flight, 16 images to a
+ * launch; a launch with a compression 8 image runs the kernel compiled with Deflate (a wave's
+ * Huffman tables in LDS), any other the one without. The context owns the LZW string tables (16 KB
+ * a lane, LZW images only) and the lanes' chunk buffers (tiles and chunky chunks; at most 1 GiB),
+ * grown on demand, one set per stream, shared with lt_tiff_decode_strips_dev. A failing chunk's
+ * pixels are unspecified; every other chunk is decoded. */
 int lt_tiff_decode_chunks_dev(lt_ctx* ctx, const lt_chunks_job* jobs, int n_jobs, void* stream);
 
 /* ---- output: TIFF strips encoded on the device (an added export of ABI 8) -------------------------

@@ -306,9 +306,8 @@ struct lt_ctx {
   // analyze kernel drops from 12.3 to 9.0-9.3 ms per 16.8 Mpx tile, but the expand kernel takes
   // 8.1 ms alone (28 GB of rows at 3.5 TB/s) and gets CU slots only between analyze launches
   bool tl_split = false;
-  lt::DecodeScratch dec;  // the strip decoder's scratch (lt_decode.hip)
+  lt::DecodeScratch dec;  // the TIFF decoder's scratch (lt_chunks.hip)
   lt::EncodeScratch enc;  // the strip encoder's scratch (lt_encode.hip)
-  lt::ChunkScratch chk;   // the chunk decoder's scratch (lt_chunks.hip)
 };
 
 static int fail(lt_ctx* c, int code, const char* fmt, const char* detail = "") {
@@ -320,23 +319,15 @@ static int fail(lt_ctx* c, int code, const char* fmt, const char* detail = "") {
   return code;
 }
 
-namespace lt {  // the context as lt_decode.hip and lt_encode.hip see it (lt_launch.h)
+namespace lt {  // the context as lt_chunks.hip and lt_encode.hip see it (lt_launch.h)
 DecodeScratch& ctx_decode(lt_ctx* c) { return c->dec; }
 EncodeScratch& ctx_encode(lt_ctx* c) { return c->enc; }
-ChunkScratch& ctx_chunks(lt_ctx* c) { return c->chk; }
 int ctx_device(const lt_ctx* c) { return c->device; }
 const lsq_xf* ctx_xtab(const lt_ctx* c) { return c->d_xtab; }
 int ctx_fail(lt_ctx* c, int code, const char* fmt, const char* detail) {
   return fail(c, code, fmt, detail);
 }
 }  // namespace lt
-
-#define HIP_OR_FAIL(ctx, expr)                                       \
-  do {                                                               \
-    hipError_t e_ = (expr);                                          \
-    if (e_ != hipSuccess) return fail(ctx, LT_ERR_HIP, #expr ": %s", \
-                                      hipGetErrorString(e_));        \
-  } while (0)
 
 extern "C" {
 
@@ -434,9 +425,8 @@ int lt_ctx_destroy(lt_ctx* c) {
   if (c->d_ndefer) (void)hipFree(c->d_ndefer);
   if (c->d_scene) (void)hipFree(c->d_scene);
   if (c->d_xtab) (void)hipFree(c->d_xtab);
-  lt::decode_release(c->dec);
-  lt::encode_release(c->enc);
-  lt::chunks_release(c->chk);
+  c->dec.release();
+  c->enc.release();
   for (auto& kv : c->index_fns) {
     if (kv.second->mod) (void)hipModuleUnload(kv.second->mod);
     delete kv.second;

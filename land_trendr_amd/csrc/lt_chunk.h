@@ -1,5 +1,5 @@
-// lt_chunk.h — one strip or tile of one TIFF image, decoded into the image's band planes: what
-// lt_decode.hip's decode_strip does for strips, for both layouts and with Deflate beside LZW.
+// lt_chunk.h — one strip or tile of one TIFF image, decoded into the image's band planes: the one
+// per-chunk decoder, for both layouts, uncompressed, LZW or Deflate.
 // Compiled for the host (g++: lt_io.cpp's lt_tiff_decode_chunks, a pool of threads) and for the
 // device (hipcc: lt_chunks.hip, one lane per chunk).
 //
@@ -115,8 +115,10 @@ LT_LZW_HD inline void undo_pred2(uint8_t* buf, int64_t rows, int64_t width, int 
   }
 }
 
-// Chunk k of image J. Returns 0 or the decoder's negative LT_IO_ERR_*.
-template <class LzwTable, class InfTable>
+// Chunk k of image J. Returns 0 or the decoder's negative LT_IO_ERR_*. kInflate false: compiled
+// without the Deflate core (its frame and Huffman tables cost the device every lane's registers,
+// scratch and LDS), for callers that hold no compression 8 image; one met all the same fails.
+template <bool kInflate = true, class LzwTable, class InfTable>
 LT_LZW_HD inline int decode_chunk(const Image& J, int64_t k, const LzwTable lzw,
                                   const InfTable inf, uint8_t* tmp) {
   const int bps = J.bps;
@@ -142,7 +144,8 @@ LT_LZW_HD inline int decode_chunk(const Image& J, int64_t k, const LzwTable lzw,
   if (J.compression == 5) {
     n = lt_lzw::decode(src, (int64_t)cnt, dst, size, lzw);
   } else if (J.compression == 8) {
-    n = lt_inflate::decode(src, (int64_t)cnt, dst, size, inf);
+    if constexpr (kInflate) n = lt_inflate::decode(src, (int64_t)cnt, dst, size, inf);
+    else return lt_lzw::kErrData;
   } else {
     n = size < (int64_t)cnt ? size : (int64_t)cnt;
     for (int64_t i = 0; i < n; i++) dst[i] = src[i];

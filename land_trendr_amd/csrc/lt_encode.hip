@@ -26,7 +26,7 @@ namespace {
 
 constexpr int kWave = 64;
 constexpr int kMaxJobs = 16;                         // rasters per launch (the argument block)
-constexpr int64_t kMaxLanes = lt::EncodeScratch::kMaxLanes;  // in flight: 1 GiB of dictionaries
+constexpr int64_t kMaxLanes = lt::EncodeSet::kMaxLanes;  // in flight: 1 GiB of dictionaries
 constexpr int64_t kSlotScratch = (int64_t)1 << 30;   // encoded strips in flight, bytes
 constexpr int kScanThreads = 1024;
 constexpr int kPackThreads = 256;
@@ -217,27 +217,6 @@ int64_t job_strips(const lt_encode_job& J) {
 
 }  // namespace
 
-namespace lt {
-
-void encode_release(EncodeScratch& s) {
-  for (int k = 0; k < s.n_sets; k++) {
-    if (s.set[k].d_tables) (void)hipFree(s.set[k].d_tables);
-    if (s.set[k].d_slots) (void)hipFree(s.set[k].d_slots);
-    if (s.set[k].d_meta) (void)hipFree(s.set[k].d_meta);
-    s.set[k] = EncodeScratch::Set();
-  }
-  s.n_sets = 0;
-}
-
-}  // namespace lt
-
-#define HIP_OR_FAIL(ctx, expr)                                               \
-  do {                                                                       \
-    hipError_t e_ = (expr);                                                  \
-    if (e_ != hipSuccess)                                                    \
-      return lt::ctx_fail(ctx, LT_ERR_HIP, #expr ": %s", hipGetErrorString(e_)); \
-  } while (0)
-
 extern "C" int lt_tiff_encode_strips_dev(lt_ctx* c, const lt_encode_job* jobs, int n_jobs,
                                          void* stream_) {
   if (!c) return LT_ERR_ARG;
@@ -289,37 +268,14 @@ extern "C" int lt_tiff_encode_strips_dev(lt_ctx* c, const lt_encode_job* jobs, i
     lanes = kSlotScratch / (slot_stride * kWave) * kWave;
     if (lanes < kWave) lanes = kWave;
   }
-  lt::EncodeScratch& E = lt::ctx_encode(c);
-  int si = -1;
-  for (int k = 0; k < E.n_sets; k++)
-    if (E.stream[k] == st) si = k;
-  if (si < 0) {
-    if (E.n_sets == lt::EncodeScratch::kMaxSets) {  // more streams than sets: start over
-      HIP_OR_FAIL(c, hipDeviceSynchronize());
-      lt::encode_release(E);
-    }
-    si = E.n_sets++;
-    E.stream[si] = st;
-    E.set[si] = lt::EncodeScratch::Set();
-  }
-  lt::EncodeScratch::Set& S = E.set[si];
+  lt::EncodeSet* Sp;
+  HIP_OR_FAIL(c, lt::ctx_encode(c).find(st, &Sp));
+  lt::EncodeSet& S = *Sp;
   if (!S.d_meta)  // per lane a size and an offset, then per job a running total and an error word
     HIP_OR_FAIL(c, hipMalloc((void**)&S.d_meta, (size_t)(kMaxLanes * 12 + kMaxJobs * 12)));
-  if (S.table_lanes < lanes) {  // (hipFree waits for the launches still using it)
-    if (S.d_tables) HIP_OR_FAIL(c, hipFree(S.d_tables));
-    S.d_tables = nullptr;
-    S.table_lanes = 0;
-    HIP_OR_FAIL(c, hipMalloc((void**)&S.d_tables,
-                             (size_t)lanes * lt_lzw::kEncSlots * sizeof(uint32_t)));
-    S.table_lanes = lanes;
-  }
-  if (S.slots_bytes < lanes * slot_stride) {
-    if (S.d_slots) HIP_OR_FAIL(c, hipFree(S.d_slots));
-    S.d_slots = nullptr;
-    S.slots_bytes = 0;
-    HIP_OR_FAIL(c, hipMalloc((void**)&S.d_slots, (size_t)(lanes * slot_stride)));
-    S.slots_bytes = lanes * slot_stride;
-  }
+  HIP_OR_FAIL(c, lt::grow(S.d_tables, S.tables_bytes,
+                          lanes * lt_lzw::kEncSlots * (int64_t)sizeof(uint32_t)));
+  HIP_OR_FAIL(c, lt::grow(S.d_slots, S.slots_bytes, lanes * slot_stride));
   int64_t* const slot_off = (int64_t*)S.d_meta;
   int64_t* const carry = slot_off + kMaxLanes;
   int32_t* const slot_size = (int32_t*)(carry + kMaxJobs);

@@ -419,7 +419,7 @@ int64_t lt_tiff_encode_strips(const uint8_t* in, int bands, int64_t rows, int64_
   return total;
 }
 
-// The decoder core the device runs (lt_lzw_core.h, lt_decode.hip), compiled for the host: what the
+// The decoder core the device runs (lt_lzw_core.h, lt_chunks.hip), compiled for the host: what the
 // CPU tests drive, and the place to look when a device decode misbehaves (the same source).
 int64_t lt_lzw_decode_core(const uint8_t* in, int64_t n_in, uint8_t* out, int64_t cap) {
   uint32_t table[4096];

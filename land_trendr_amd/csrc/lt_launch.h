@@ -1,5 +1,5 @@
 // lt_launch.h — what lt_abi.hip hands the analyze-stage dispatch for one tile, and what it shares
-// with the strip decoder (lt_decode.hip) and the strip encoder (lt_encode.hip).
+// with the TIFF decoder (lt_chunks.hip) and the strip encoder (lt_encode.hip).
 //
 // The kernels of the analyze and resolve stages (lt_kernels.h) are instantiated in a dispatch
 // translation unit of their own: lt_dispatch.hip in the product library, a profiling unit in the
@@ -30,63 +30,98 @@ struct TileLaunch {
   double* tl_eqn = nullptr;      // its segment eqns ([Y-1][n_pix] (m, b) pairs)
 };
 
-// The strip decoder's share of a context (lt_decode.hip, lt_tiff_decode_strips_dev): scratch grown
-// on demand, freed with the context (decode_release, called by lt_ctx_destroy). One set per stream
-// the decoder was called on: launches on one stream run one after the other and share a set, while
-// several rasters decode side by side on streams of their own.
-struct DecodeScratch {
-  struct Set {
-    uint32_t* d_tables = nullptr;  // the lanes' LZW string tables: [waves][4096 entries][64 lanes]
-    int64_t table_lanes = 0;
-    uint8_t* d_strips = nullptr;   // chunky images: one decoded strip per lane (de-interleaved
-    int64_t strips_bytes = 0;      // from there)
-  };
+// Scratch a context keeps for the TIFF decoder and encoder: grown on demand, freed with the context
+// (release, called by lt_ctx_destroy). One set per stream an entry was called on: launches on one
+// stream run one after the other and share a set, while several rasters are decoded or encoded
+// side by side on streams of their own.
+template <class Set>
+struct StreamSets {
   static constexpr int kMaxSets = 16;
   hipStream_t stream[kMaxSets] = {};
   Set set[kMaxSets];
   int n_sets = 0;
+  void release() {
+    for (int k = 0; k < n_sets; k++) {
+      set[k].release();
+      set[k] = Set();
+    }
+    n_sets = 0;
+  }
+  // this stream's set, or a new one; more streams than sets: wait for the device and start over
+  hipError_t find(hipStream_t st, Set** out) {
+    for (int k = 0; k < n_sets; k++)
+      if (stream[k] == st) {
+        *out = &set[k];
+        return hipSuccess;
+      }
+    if (n_sets == kMaxSets) {
+      const hipError_t e = hipDeviceSynchronize();
+      if (e != hipSuccess) return e;
+      release();
+    }
+    stream[n_sets] = st;
+    set[n_sets] = Set();
+    *out = &set[n_sets++];
+    return hipSuccess;
+  }
 };
-void decode_release(DecodeScratch& s);
-// The strip encoder's share of a context (lt_encode.hip, lt_tiff_encode_strips_dev): scratch grown
-// on demand, freed with the context (encode_release), one set per stream like the decoder's.
-struct EncodeScratch {
-  struct Set {
-    uint32_t* d_tables = nullptr;  // the lanes' LZW dictionaries: [waves][8192 slots][64 lanes]
-    int64_t table_lanes = 0;
-    uint8_t* d_slots = nullptr;    // one worst-case encoded strip per lane
-    int64_t slots_bytes = 0;
-    void* d_meta = nullptr;        // per lane a size and an offset, per job a total and an error
-  };
-  static constexpr int kMaxSets = 16;
+// the device buffer `d` of `have` bytes grown to at least n, its contents dropped (hipFree waits
+// for the launches still using it)
+template <class T>
+inline hipError_t grow(T*& d, int64_t& have, int64_t n) {
+  if (have >= n) return hipSuccess;
+  if (d) {
+    const hipError_t e = hipFree(d);
+    if (e != hipSuccess) return e;
+  }
+  d = nullptr;
+  have = 0;
+  const hipError_t e = hipMalloc((void**)&d, (size_t)n);
+  if (e == hipSuccess) have = n;
+  return e;
+}
+// The TIFF decoder's set (lt_chunks.hip; lt_tiff_decode_strips_dev and lt_tiff_decode_chunks_dev
+// share it).
+struct DecodeSet {
+  uint32_t* d_tables = nullptr;  // LZW images: the lanes' string tables,
+  int64_t tables_bytes = 0;      // [waves][4096 entries][64 lanes]
+  uint8_t* d_chunks = nullptr;   // tiles and chunky chunks: one decoded chunk per lane (copied
+  int64_t chunks_bytes = 0;      // into the planes from there)
+  void release() {
+    if (d_tables) (void)hipFree(d_tables);
+    if (d_chunks) (void)hipFree(d_chunks);
+  }
+};
+using DecodeScratch = StreamSets<DecodeSet>;
+// The strip encoder's set (lt_encode.hip, lt_tiff_encode_strips_dev).
+struct EncodeSet {
   static constexpr int64_t kMaxLanes = 32768;  // in flight: 1 GiB of dictionaries
-  hipStream_t stream[kMaxSets] = {};
-  Set set[kMaxSets];
-  int n_sets = 0;
+  uint32_t* d_tables = nullptr;  // the lanes' LZW dictionaries: [waves][8192 slots][64 lanes]
+  int64_t tables_bytes = 0;
+  uint8_t* d_slots = nullptr;    // one worst-case encoded strip per lane
+  int64_t slots_bytes = 0;
+  void* d_meta = nullptr;        // per lane a size and an offset, per job a total and an error
+  void release() {
+    if (d_tables) (void)hipFree(d_tables);
+    if (d_slots) (void)hipFree(d_slots);
+    if (d_meta) (void)hipFree(d_meta);
+  }
 };
-void encode_release(EncodeScratch& s);
-// The chunk decoder's share of a context (lt_chunks.hip, lt_tiff_decode_chunks_dev): scratch grown
-// on demand, freed with the context (chunks_release), one set per stream like the strip decoder's.
-struct ChunkScratch {
-  struct Set {
-    uint32_t* d_tables = nullptr;  // LZW images: the lanes' string tables, as DecodeScratch's
-    int64_t table_lanes = 0;
-    uint8_t* d_chunks = nullptr;   // tiles and chunky chunks: one decoded chunk per lane
-    int64_t chunks_bytes = 0;
-  };
-  static constexpr int kMaxSets = 16;
-  hipStream_t stream[kMaxSets] = {};
-  Set set[kMaxSets];
-  int n_sets = 0;
-};
-void chunks_release(ChunkScratch& s);
-// What lt_decode.hip and lt_encode.hip need of a context (defined in lt_abi.hip beside lt_ctx).
+using EncodeScratch = StreamSets<EncodeSet>;
+// What lt_chunks.hip and lt_encode.hip need of a context (defined in lt_abi.hip beside lt_ctx).
 DecodeScratch& ctx_decode(lt_ctx* c);
 EncodeScratch& ctx_encode(lt_ctx* c);
-ChunkScratch& ctx_chunks(lt_ctx* c);
 int ctx_device(const lt_ctx* c);
 // the context's x-set factor table (lt_lapack.h), as the fit-to-vertex kernel reads it (lt_ftv.hip)
 const lsq_xf* ctx_xtab(const lt_ctx* c);
 int ctx_fail(lt_ctx* c, int code, const char* fmt, const char* detail);
+// (in the entry points: a failing HIP call ends the entry with LT_ERR_HIP and its message)
+#define HIP_OR_FAIL(ctx, expr)                                                   \
+  do {                                                                           \
+    hipError_t e_ = (expr);                                                      \
+    if (e_ != hipSuccess)                                                        \
+      return lt::ctx_fail(ctx, LT_ERR_HIP, #expr ": %s", hipGetErrorString(e_)); \
+  } while (0)
 
 // Stage 1: the analyze kernel over every pixel of the tile, on l.stream.
 hipError_t launch_analyze(const TileLaunch& l);

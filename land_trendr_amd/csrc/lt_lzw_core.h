@@ -1,6 +1,6 @@
 // lt_lzw_core.h — one TIFF LZW strip decoder and one encoder (below it), compiled for the host
 // (g++: lt_io.cpp's lt_lzw_decode_core / lt_lzw_encode_core) and for the device (hipcc:
-// lt_decode.hip and lt_encode.hip, one lane per strip).
+// lt_chunks.hip and lt_encode.hip, one lane per strip).
 //
 // The stream rules are those at the top of lt_io.cpp: codes MSB first, 9 to 12 bits wide, Clear 256,
 // EOI 257, first free code 258, libtiff's early change, a strip may end without EOI, data starts

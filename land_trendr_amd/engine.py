@@ -717,7 +717,7 @@ class Engine:
                                                 ctypes.c_void_p(st.cuda_stream)),
                     'lt_raster_assemble')
 
-    # --- ingest: TIFF strips decoded on the device (lt_tiff_decode_strips_dev, lt_decode.hip) ---
+    # --- ingest: TIFF strips decoded on the device (lt_tiff_decode_strips_dev, lt_chunks.hip) ---
     def decode_strips(self, jobs, stream=None):
         """Every strip of len(jobs) strip-organised TIFF images whose compressed bytes are in
         device memory, decoded by the HIP strip decoder in one call. A job is a dict:

@@ -202,21 +202,13 @@ class GeoTiff:
 
 
     def device_eligible(self):
-        """Whether read_device takes this file: strip-organised, uncompressed or LZW, predictor 1
-        (or 2 with integer samples), 8/16/32/64-bit samples, strips that decode to less than
-        1 MiB (the device decoder's table packs 20-bit positions, lt_lzw_core.h)."""
-        t = self.tags
-        if 273 not in t or 279 not in t or self.compression not in (1, 5):
-            return False
-        if not (self.predictor == 1 or (self.predictor == 2 and self.dtype.kind in 'iu')):
-            return False
-        if self.bits not in (8, 16, 32, 64) or self.planar not in (1, 2):
-            return False
-        if self.width <= 0 or self.height <= 0 or self.bands <= 0:
-            return False
-        rps = min(int(t.get(278, (self.height,))[0]), self.height)
-        spp = self.bands if self.planar == 1 else 1
-        return 0 < rps and rps * self.width * spp * self.dtype.itemsize < (1 << 20)
+        """Whether read_device takes this file: the strip-organised, uncompressed or LZW files
+        among device_chunks_eligible()'s (predictor 1, or 2 with integer samples, 8/16/32/64-bit
+        samples, strips that decode to less than 1 MiB: the device decoder's table packs 20-bit
+        positions, lt_lzw_core.h)."""
+        lay = self.chunk_layout()
+        return (lay is not None and not lay[4] and self.compression in (1, 5) and
+                self.device_chunks_eligible())
 
     def read_device(self, engine, out=None, stream=None, check=True, staging=None):
         """read() on the GPU: the byte range that spans the strips is copied from the mapping into
@@ -229,27 +221,18 @@ class GeoTiff:
         has run, and leaves `staging` alone until the event self.staged (recorded behind the copy
         to the device) has completed. A file that is not device_eligible()
         raises TiffError and nothing is decoded. Returns (out, error word)."""
-        if not self.device_eligible():
-            raise TiffError('not eligible for the device decoder (GeoTiff.device_eligible)')
-        t = self.tags
-        H, B = self.height, self.bands
-        rps = min(int(t.get(278, (H,))[0]), H)
-        per_band = -(-H // rps)
-        need = per_band if self.planar == 1 else per_band * B
+        return self._read_device(self.device_eligible, engine, 'decode_strips', out, stream, check,
+                                 staging)
 
-        def decode(file, offsets, counts, st):
-            return engine.decode_strips([dict(
-                file=file, offsets=offsets, counts=counts,
-                compression=self.compression, predictor=self.predictor, dtype=self.dtype,
-                width=self.width, height=H, bands=B, planar=self.planar, rows_per_strip=rps,
-                out=out)], stream=st)
-        return self._staged_decode(engine, t[273], t[279], need, decode, stream, check, staging,
-                                   'strips')
-
-    def _staged_decode(self, engine, offsets, counts, need, decode, stream, check, staging, what):
-        """read_device's and read_device_chunks's common part: the byte range that spans the first
-        `need` chunks into `staging`, the offsets and counts behind it, one copy to the device,
-        the event self.staged, then decode(file, offsets, counts, stream) -> (outs, err)."""
+    def _read_device(self, eligible, engine, method, out, stream, check, staging):
+        """read_device and read_device_chunks: the eligibility test, the byte range that spans the
+        image's chunks into `staging`, the offsets and counts behind it, one copy to the device,
+        the event self.staged, then the engine's `method` on one job (which names the layout both
+        ways: each engine method reads its own keys)."""
+        if not eligible():  # (before the engine is touched)
+            raise TiffError('not eligible for the device decoder (GeoTiff.%s)' % eligible.__name__)
+        otag, ctag, cw, ch, tiled, need = self.chunk_layout()
+        offsets, counts, what = self.tags[otag], self.tags[ctag], 'tiles' if tiled else 'strips'
         import torch
         from .engine import LtError
         offs = np.asarray(offsets, np.int64)
@@ -282,7 +265,11 @@ class GeoTiff:
                 self.staged = torch.cuda.Event()
                 self.staged.record(st)
                 dt = d[n8:].view(torch.int64)
-                outs, err = decode(d[:n] if n else d[:0], dt[:len(offs)], dt[len(offs):], st)
+                outs, err = getattr(engine, method)([dict(
+                    file=d[:n] if n else d[:0], offsets=dt[:len(offs)], counts=dt[len(offs):],
+                    compression=self.compression, predictor=self.predictor, dtype=self.dtype,
+                    width=self.width, height=self.height, bands=self.bands, planar=self.planar,
+                    rows_per_strip=ch, chunk_w=cw, chunk_h=ch, tiled=tiled, out=out)], stream=st)
         except LtError as e:
             raise TiffError(str(e))
         if check:
@@ -334,19 +321,8 @@ class GeoTiff:
         """read_device for every device_chunks_eligible() file (tiles, Deflate; strips and LZW as
         well), decoded by engine.decode_chunks: the same staging, `staged` event, error word and
         return. A file that is not eligible raises TiffError before the engine is touched."""
-        if not self.device_chunks_eligible():
-            raise TiffError('not eligible for the device chunk decoder '
-                            '(GeoTiff.device_chunks_eligible)')
-        otag, ctag, cw, ch, tiled, need = self.chunk_layout()
-
-        def decode(file, offsets, counts, st):
-            return engine.decode_chunks([dict(
-                file=file, offsets=offsets, counts=counts,
-                compression=self.compression, predictor=self.predictor, dtype=self.dtype,
-                width=self.width, height=self.height, bands=self.bands, planar=self.planar,
-                chunk_w=cw, chunk_h=ch, tiled=tiled, out=out)], stream=st)
-        return self._staged_decode(engine, self.tags[otag], self.tags[ctag], need, decode, stream,
-                                   check, staging, 'tiles' if tiled else 'strips')
+        return self._read_device(self.device_chunks_eligible, engine, 'decode_chunks', out, stream,
+                                 check, staging)
 
     def staging_bytes(self):
         """An upper bound of the pinned bytes read_device / read_device_chunks stage."""

@@ -529,12 +529,8 @@ class LocalJob:
         what = 'strips or tiles' if self.device_formats == 'all' else 'strips'
         # device_formats: which files are offered to the device, and the reader that takes them
         eligible = self.device_takes
-        if self.device_formats == 'all':
-            def read_device(ds, **kw):
-                return ds.read_device_chunks(eng, **kw)
-        else:
-            def read_device(ds, **kw):
-                return ds.read_device(eng, **kw)
+        read_device = (GeoTiff.read_device_chunks if self.device_formats == 'all'
+                       else GeoTiff.read_device)
 
         class Dec:
             def __init__(self):
@@ -568,7 +564,7 @@ class LocalJob:
                             tl.scratch = torch.empty(n, dtype=torch.uint8, device=up.device)
                     tdt = torch.from_numpy(np.empty(0, ds.dtype.newbyteorder('='))).dtype
                     out = tl.scratch[:n].view(tdt).view(ds.bands, ds.height, ds.width)
-                _, err = read_device(ds, out=out, stream=tl.stream, check=False,
+                _, err = read_device(ds, eng, out=out, stream=tl.stream, check=False,
                                      staging=tl.staging)
                 t3 = time.perf_counter()
                 tl.staged = ds.staged

@@ -1,6 +1,6 @@
 """The device decoders' rate alone, in GB/s of decoded bytes, for one raster of each kind: LZW
-strips through the strip decoder (GeoTiff.read_device) and through the chunk decoder
-(read_device_chunks), Deflate strips, Deflate tiles. The raster is two int16 bands of a synthetic
+strips through the strips entry (GeoTiff.read_device; the row still named "strip decoder") and
+through the chunks entry (read_device_chunks), which share one kernel; Deflate strips, Deflate tiles. The raster is two int16 bands of a synthetic
 scene (tools/job_bench.py's rasters). kernel_ms: the decode call between two events on its
 stream, the file's bytes already on the device; read_call_ms: the whole read_device /
 read_device_chunks call with check=True (staging copy, H2D, kernel, synchronise). Best of --reps.
