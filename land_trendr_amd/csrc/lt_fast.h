@@ -224,8 +224,11 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
   __syncthreads();  // one wave per workgroup: orders the table writes before any lane reads
 
   // ---- pick_winners (utils.py:491-521) over wave-uniform year slots ----
+  // the pixel's point masks (lt_bits.h): 32 bits in the instances of at most 32 years, where
+  // every year slot, point index and vertex number is below 32 (T = n = 32 uses bit 31 of each)
+  typedef typename PointBits<MAXY>::type PM;
   int T = 0, y0 = 0;
-  uint64_t pres = 0;  // year slots with a winner: present point t is the t-th set bit
+  PM pres = 0;  // year slots with a winner: present point t is the t-th set bit
   // int16 series: the values are integers of int16 range, so despike's standard deviation is
   // compared through the exact sums S = sum v, Q = sum v^2 (see the despike below)
   constexpr bool kIntSeries = std::is_same<VT, int16_t>::value;
@@ -489,7 +492,7 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
           const double vp = pr ? v : 0.0;
           Ssum += vp;
           Qsum = __builtin_fma(vp, vp, Qsum);
-          pres |= pr ? 1ull << y : 0ull;
+          pres |= pr ? LT_PB_BIT(PM, y) : (PM)0;
           T += pr ? 1 : 0;
           continue;
         }
@@ -519,7 +522,7 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
           Ssum += v;
           Qsum = __builtin_fma(v, v, Qsum);
         }
-        pres |= 1ull << y;
+        pres |= LT_PB_BIT(PM, y);
         T++;
         if (LT_OUTF(out, val_raw))
           __builtin_nontemporal_store(v, LT_OUTF(out, val_raw) + q);
@@ -537,7 +540,7 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
   const int Tmax = wave_max(ok ? T : 0);
 
   // ---- despike (utils.py:556-582): numpy pairwise std, then the 3-window scan ----
-  uint64_t spike = 0;
+  PM spike = 0;
   int n = 0;
   if (kIntSeries && Tmax >= 2) {
     // int16 series. The reference's sd is numpy's (pairwise sums of v and of (avg - v)^2, below
@@ -617,7 +620,7 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
         last_good = is_spike ? last_good : yv;  // (a lane past its points never reads it)
         xv = yv;
         yv = zv;
-        spike |= is_spike ? (1ull << t) : 0ull;
+        spike |= is_spike ? LT_PB_BIT(PM, t) : (PM)0;
         // slot n gets point t; n moves on for a kept point (slot n = t before the first spike:
         // the same values rewritten)
         L.ys[n][lane] = (VT)cur;
@@ -670,12 +673,12 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
                                      (double)T);
     // the 3-window scan (on the original series) fused with dropna's in-place compaction: point
     // t is written to slot n <= t once its spike decision is known; ys[t + 1] is read first
-    uint64_t rem = pres;
+    PM rem = pres;
     double last_good = ok ? L.ys[0][lane] : 0.0;
     double xv = last_good, yv = ok ? L.ys[1][lane] : 0.0;
     if (ok) {  // point 0 is never a spike
-      const int y = __builtin_ctzll(rem);
-      rem &= rem - 1;
+      const int y = LT_PB_CTZ(PM, rem);
+      rem = LT_PB_DROP_LOWEST(PM, rem);
       L.xn[0][lane] = (uint8_t)(L.year[y] - y0);
       n = 1;
     }
@@ -701,10 +704,10 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
           xv = yv;
           yv = zv;
         }
-        const int y = __builtin_ctzll(rem);
-        rem &= rem - 1;
+        const int y = LT_PB_CTZ(PM, rem);
+        rem = LT_PB_DROP_LOWEST(PM, rem);
         if (is_spike) {
-          spike |= 1ull << t;
+          spike |= LT_PB_BIT(PM, t);
           continue;
         }
         if (n != t) L.ys[n][lane] = (VT)cur;
@@ -719,7 +722,7 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
 
   // ---- segmented least squares DP (utils.py:618-631), decided lazily ----
   bool deferred = live && T >= 2 && f32_bad;
-  uint64_t vmask = 0;  // vertices over non-spike indices
+  PM vmask = 0;  // vertices over non-spike indices
   // DP argmin of each column (see WaveLds): written at wave-uniform columns, read once per vertex
   // by the backtrack
   uint8_t AG[EXACT ? 1 : MAXY];
@@ -750,7 +753,7 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
         double H = inf;
         // starts whose interval reaches the smallest upper end seen so far (itself included): a
         // superset of those reaching the final one, where the exact minimum lies
-        uint64_t cand = 0;
+        PM cand = 0;
         {
           const double yj = (double)L.ys[j][lane];
           SyyAll = __builtin_fma(yj, yj, SyyAll);
@@ -790,20 +793,20 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
           }
           const double v = (e + c) + oi;
           if (m >= 3) w = __builtin_fma(0x1p-50, __builtin_fabs(v), kScreen * Syy);
-          if (v - w <= H) cand |= 1ull << i;
+          if (v - w <= H) cand |= LT_PB_BIT(PM, i);
           H = v + w < H ? v + w : H;
           // early exit (dp_start_bound): no start below i can reach H
           if (prune && m >= 3 && !__ballot(col && !(dp_start_bound(e, oi, 0.0, c, SyyAll) > H)))
             break;
         }
-        const int nc = col ? __builtin_popcountll(cand) : 0;
+        const int nc = col ? LT_PB_POPC(PM, cand) : 0;
         const int ncmax = wave_max(nc);
         double best = inf;
         int bi = 0;
         for (int r = 0; r < ncmax; r++) {  // candidates in increasing start order, lockstep
           const bool act = r < nc;
-          const int i = act ? __builtin_ctzll(cand) : 0;
-          if (act) cand &= cand - 1;
+          const int i = act ? LT_PB_CTZ(PM, cand) : 0;
+          if (act) cand = LT_PB_DROP_LOWEST(PM, cand);
           const double oi = OPT[i];  // per-lane index, loaded before the fit that hides it
           const int m = j - i + 1;
           const bool ls = act && m >= 3;
@@ -847,7 +850,7 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
         double H = inf;
         // starts whose interval reaches the smallest upper end seen so far (itself included): a
         // superset of those reaching the final one, where the exact minimum lies
-        uint64_t cand = 0;
+        PM cand = 0;
         {
           const double yj = (double)L.ys[j][lane];
           SyyAll = __builtin_fma(yj, yj, SyyAll);
@@ -877,20 +880,20 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
           }
           const double v = (e + c) + OPT[i];
           if (m >= 3) w = __builtin_fma(0x1p-50, __builtin_fabs(v), kScreen * Syy);
-          if (v - w <= H) cand |= 1ull << i;
+          if (v - w <= H) cand |= LT_PB_BIT(PM, i);
           H = v + w < H ? v + w : H;
           // early exit (dp_start_bound): no start below i can reach H
           if (prune && m >= 3 && !__ballot(col && !(dp_start_bound(e, OPT[i], 0.0, c, SyyAll) > H)))
             break;
         }
-        const int nc = col ? __builtin_popcountll(cand) : 0;
+        const int nc = col ? LT_PB_POPC(PM, cand) : 0;
         const int ncmax = wave_max(nc);
         double best = inf;
         int bi = 0;
         for (int r = 0; r < ncmax; r++) {  // candidates in increasing start order, lockstep
           const bool act = r < nc;
-          const int i = act ? __builtin_ctzll(cand) : 0;
-          if (act) cand &= cand - 1;
+          const int i = act ? LT_PB_CTZ(PM, cand) : 0;
+          if (act) cand = LT_PB_DROP_LOWEST(PM, cand);
           const int m = j - i + 1;
           const bool ls = act && m >= 3;
           double e = 0.0;
@@ -923,10 +926,10 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
       }
     }
     if (n >= 1) {
-      vmask = 1ull << (n - 1);
+      vmask = LT_PB_BIT(PM, n - 1);
       for (int j = n - 1; j >= 0;) {
         const int a = ag_get(j);
-        vmask |= 1ull << a;
+        vmask |= LT_PB_BIT(PM, a);
         j = a - 1;
       }
     }
@@ -935,7 +938,10 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
     const double inf = __builtin_inf();
     double OPTa[MAXY + 1];  // per-lane private memory (wave-uniform indices)
     OPTa[0] = 0.0;
-    uint64_t exact = 1;      // bit k: OPTa[k] is the reference value itself
+    // bit k: OPTa[k] is the reference value itself. Bits 0..n-1 only are read (a start i <= j <
+    // n reads bit i); column j sets bit j+1, and in a 32-bit mask the bit of column 31, which
+    // would describe OPTa[32], the total no start reads, is dropped by the shift
+    PM exact = 1;
     double Emax = 0.0;       // bound on |OPTa[k] - OPT[k]| for every inexact k so far
     // register window of the four most recent points (x, y of points j..j-3) and of OPTa[j..j-3]:
     // the 1- to 4-point starts of a column, nearly all the DP prices, read no LDS or private
@@ -973,7 +979,7 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
     const bool zok = c > 0.0;
     const bool zlane = zok && intdata;
     const uint64_t zmask = __ballot(zlane);
-    uint64_t amb = 0;
+    PM amb = 0;
     // column j: wx0 receives point j (its slot held point j-4); wx1..wx3 hold points j-1..j-3;
     // opt_j..opt_jm3 hold OPTa[j..j-3] (tags tg_*), and OPTa[j+1] is written over opt_jm3
     auto column = [&](const int j, int& wx0, int& wx1, int& wx2, int& wx3, double& wy0,
@@ -1350,7 +1356,7 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
         // its half-width, rounded up: Hi = fl(v1 + w1) >= v1 + w1 - ulp(Hi) / 2
         enew = __builtin_fma(Hi - v1, 1.0 + 0x1p-50, 0x1p-50 * __builtin_fabs(Hi));
       } else {  // ambiguous: the pixel goes to the resolve stage if its optimal path comes here
-        if (col) amb |= 1ull << j;
+        if (col) amb |= LT_PB_BIT(PM, j);
         a = v1 <= Ve ? i1 : ie;
         vnew = v1 <= Ve ? v1 : Ve;
         tnew = (j + 1) << 8;
@@ -1360,7 +1366,7 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
       if (col) {
         ag_set(j, a);
         OPTa[j + 1] = vnew;  // wave-uniform index
-        if (tnew < 256) exact |= 2ull << j;
+        if (tnew < 256) exact |= LT_PB_TWO(PM, j);  // (j = 31 of a 32-bit mask: nothing)
         Emax = __builtin_fmax(enew, Emax);
         opt_jm3 = vnew;  // OPTa[j+1]: the slot of OPTa[j-3], which no later column reads
         tg_jm3 = tnew;
@@ -1378,11 +1384,11 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
     }
     // find_segments (utils.py:633-644): starts of the optimal segments + the last point
     if (n >= 1) {
-      vmask = 1ull << (n - 1);
+      vmask = LT_PB_BIT(PM, n - 1);
       for (int j = n - 1; j >= 0;) {
         const int a = ag_get(j);
         if ((amb >> j) & 1) deferred = true;
-        vmask |= 1ull << a;
+        vmask |= LT_PB_BIT(PM, a);
         j = a - 1;
       }
     }
@@ -1439,19 +1445,19 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
     // issued, so those loads do not wait for it.
     const bool emit = live && !deferred;
     const bool good = emit && ok;
-    const uint64_t vm = good ? vmask : 0;
-    const int nv = __builtin_popcountll(vm);
+    const PM vm = good ? vmask : 0;
+    const int nv = LT_PB_POPC(PM, vm);
     const int nvmax = wave_max(nv);
-    uint64_t vrem = vm, left = 0;
+    PM vrem = vm, left = 0;
     double pm = 0.0, pb = 0.0;  // eqn of vertex q-1
     double* const eq = tl_eqn;
     const int64_t np = in.n_pix;
     for (int q = 0; q < nvmax; q++) {
       const bool act = q < nv;
-      const int ka = act ? __builtin_ctzll(vrem) : 0;
-      if (act) vrem &= vrem - 1;
+      const int ka = act ? LT_PB_CTZ(PM, vrem) : 0;
+      if (act) vrem = LT_PB_DROP_LOWEST(PM, vrem);
       const bool has_next = act && q + 1 < nv;
-      const int kb = has_next ? __builtin_ctzll(vrem) : ka;
+      const int kb = has_next ? LT_PB_CTZ(PM, vrem) : ka;
       double cm = pm, cb = pb;
       if (__ballot(has_next)) {
         double sm = 0.0, sbv = 0.0;
@@ -1478,7 +1484,7 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
         const double fl = (pm * x) + pb;
         if (__builtin_fabs(fl - raw_v) <= __builtin_fabs(fit_vertex - raw_v)) {
           fit_vertex = fl;
-          left |= 1ull << q;
+          left |= LT_PB_BIT(PM, q);
         }
       }
       if (act) offer_rules(q, y0 + L.xn[ka][lane], fit_vertex);
@@ -1486,10 +1492,11 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
       pb = cb;
     }
     if (emit) {
-      __builtin_nontemporal_store(good ? pres : 0ull, tl_bits + p);
-      __builtin_nontemporal_store(spike, tl_bits + np + p);
-      __builtin_nontemporal_store(vm, tl_bits + 2 * np + p);
-      __builtin_nontemporal_store(left, tl_bits + 3 * np + p);
+      // (the planes of the ABI are 64-bit: a narrower mask is widened here)
+      __builtin_nontemporal_store((uint64_t)(good ? pres : (PM)0), tl_bits + p);
+      __builtin_nontemporal_store((uint64_t)spike, tl_bits + np + p);
+      __builtin_nontemporal_store((uint64_t)vm, tl_bits + 2 * np + p);
+      __builtin_nontemporal_store((uint64_t)left, tl_bits + 3 * np + p);
     }
   } else if (year_out) {
     // Year-major: every year slot is one wave-uniform step and each per-year plane is written
@@ -1503,15 +1510,15 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
     // nothing (the resolve stage writes them).
     const bool emit = live && !deferred;
     const bool good = emit && ok;
-    uint64_t vrem = vmask;           // vertices not reached yet (non-spike indices)
-    uint64_t frem = vmask;           // vertices whose segment is not fitted yet (the lowest next)
+    PM vrem = vmask;                 // vertices not reached yet (non-spike indices)
+    PM frem = vmask;                 // vertices whose segment is not fitted yet (the lowest next)
     double pm = 0.0, pb = 0.0;       // eqn of the previous vertex
     double cm = 0.0, cb = 0.0;       // eqn of the current vertex (right eqn of the points)
     double nm = 0.0, nb = 0.0;       // lookahead: eqn of the segment from the next vertex
     bool have_n = false;
     // spike / vertex flags by year slot: with yflags the u8 planes are written from them by
     // year_flags_kernel (lt_abi.hip) in 256-byte rows instead of 64-byte pieces here
-    uint64_t spk = 0, vtx = 0;
+    PM spk = 0, vtx = 0;
     int t = 0, k = 0, q = 0;         // present index, non-spike index, vertex number
     // One year's row of the five binary64 planes. (A fit step's x-set table loads share the
     // in-order vector-memory counter with the stores, so a load issued after a year's stores waits
@@ -1550,15 +1557,15 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
       const bool pr = good && ((pres >> y) & 1);
       const bool sp = pr && ((spike >> t) & 1);
       const bool isv = pr && !sp && ((vrem >> k) & 1);
-      const uint64_t after = vrem & (vrem - 1);  // vertices after this one
+      const PM after = LT_PB_DROP_LOWEST(PM, vrem);  // vertices after this one
       const bool nextfit = isv && after != 0;
       double sm = 0.0, sbv = 0.0;
       bool fitnow = false;
       if (__ballot(nextfit && !have_n)) {
-        const uint64_t fnext = frem & (frem - 1);
+        const PM fnext = LT_PB_DROP_LOWEST(PM, frem);
         fitnow = fnext != 0 && (!have_n || nextfit);
-        const int kbase = fitnow ? __builtin_ctzll(frem) : 0;
-        const int kb = fitnow ? __builtin_ctzll(fnext) : 1;
+        const int kbase = fitnow ? LT_PB_CTZ(PM, frem) : 0;
+        const int kb = fitnow ? LT_PB_CTZ(PM, fnext) : 1;
         const int rc = lsq_fit_lockstep(
             fitnow, kb - kbase + 1, [&](int i) { return (int)L.xn[kbase + i][lane]; },
             [&](int i) { return (double)L.ys[kbase + i][lane]; }, xtab, sm, sbv);
@@ -1608,8 +1615,8 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
       if (emit) {
         const int64_t o = (int64_t)y * os + p;
         if (yflags) {
-          spk |= (uint64_t)sp << y;
-          vtx |= (uint64_t)isv << y;
+          spk |= (PM)sp << y;
+          vtx |= (PM)isv << y;
         } else {
           if (auto* a = LT_OUTF(out, spike)) a[o] = sp ? 1 : 0;
           if (auto* a = LT_OUTF(out, vertex)) a[o] = isv ? 1 : 0;
@@ -1621,8 +1628,8 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
       }
     }
     if (emit && yflags) {
-      yflags[p] = spk;
-      yflags[in.n_pix + p] = vtx;
+      yflags[p] = (uint64_t)spk;  // (64-bit planes: widened here)
+      yflags[in.n_pix + p] = (uint64_t)vtx;
     }
   } else if constexpr (RMAX <= LT_CERT_RULES) {
     // (the resolve stage too: c2 2387 vs 2376 Mpx/s, resolve 0.43 vs 0.46 ms, profiles/r04_run8)
@@ -1632,10 +1639,10 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
     // (kFitW), and each disturbance offered to the rules' candidate sets (lt_pixel.h RuleCands);
     // (B) lockstep over the candidates: the emulated (reference) fits of the two or three
     // segments around each, and the exact offers, in order, to the rules holding it ----
-    const int nv = __builtin_popcountll(vmask);
+    const int nv = LT_PB_POPC(PM, vmask);
     const int nvmax = wave_max(nv);
-    RuleCands cand[RMAX];
-    uint64_t vrem = vmask;  // vertices from q on: vertex q is its lowest bit
+    RuleCandsT<PM> cand[RMAX];
+    PM vrem = vmask;  // vertices from q on: vertex q is its lowest bit
     // closed-form eqn (slope, intercept, error scale) of the segment ending at vertex q-1
     double am = 0.0, ab = 0.0, asc = 0.0;
     double fprev = 0.0, wprev = 0.0;  // fitted value of vertex q-1: center, half-width
@@ -1643,7 +1650,7 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
     // interior vertices (by point index) whose fitted value certainly takes the left (CL) / the
     // right (CR) eqn: the reference's choice, decided by the closed-form intervals (pass B then
     // needs only that eqn's emulated fit there)
-    uint64_t CL = 0, CR = 0;
+    PM CL = 0, CR = 0;
     auto add_pt = [&](int k, int& Sx, int& Sxx, double& Sy, double& Sxy, double& ymx)
                       __attribute__((always_inline)) {
       const int xi = L.xn[k][lane];
@@ -1656,10 +1663,10 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
     };
     for (int q = 0; q < nvmax; q++) {
       const bool act = q < nv;
-      const int ka = act ? __builtin_ctzll(vrem) : 0;
-      if (act) vrem &= vrem - 1;
+      const int ka = act ? LT_PB_CTZ(PM, vrem) : 0;
+      if (act) vrem = LT_PB_DROP_LOWEST(PM, vrem);
       const bool has_next = act && q + 1 < nv;
-      const int kb = has_next ? __builtin_ctzll(vrem) : ka;
+      const int kb = has_next ? LT_PB_CTZ(PM, vrem) : ka;
       double cm = am, cb = ab, csc = asc;  // the last vertex reuses the previous eqn (utils.py:662)
       if (__ballot(has_next)) {
         // least squares of the points ka..kb by the closed form: two to four points straight-line,
@@ -1706,13 +1713,13 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
         if (dl + slack <= dr) {  // certainly the left eqn
           fv = fl;
           w = wl;
-          CL |= 1ull << ka;
+          CL |= LT_PB_BIT(PM, ka);
         } else if (!(dr + slack < dl)) {  // either: the hull of both intervals
           const double lo = __builtin_fmin(fl - wl, fr - wr), hi = __builtin_fmax(fl + wl, fr + wr);
           fv = 0.5 * (lo + hi);
           w = 0.5 * (hi - lo) + 0x1p-50 * (__builtin_fabs(lo) + __builtin_fabs(hi));
         } else {  // certainly the right eqn
-          CR |= 1ull << ka;
+          CR |= LT_PB_BIT(PM, ka);
         }
       }
       const int32_t yr = y0 + (int32_t)x;
@@ -1723,7 +1730,7 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
         for (int r = 0; r < RMAX; r++)
           if (r < LT_NRULES)
             cand[r].offer(LT_RULE(r), LT_PRE_MODE, yprev, yr - yprev, fprev - wprev,
-                          fprev + wprev, mag - wm, mag + wm, 1ull << ka, status);
+                          fprev + wprev, mag - wm, mag + wm, LT_PB_BIT(PM, ka), status);
       }
       am = cm;
       ab = cb;
@@ -1734,25 +1741,28 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
     }
     // (B) the candidates in increasing order; a series with an infinite value (whose emulated
     // fits fail and are flagged) replays every disturbance
-    uint64_t U = 0;
+    PM U = 0;
 #pragma unroll
     for (int r = 0; r < RMAX; r++)
       if (r < LT_NRULES) U |= cand[r].G;
-    if (infdata) U = vmask & (vmask - 1);
-    const int nu = __builtin_popcountll(U);
+    if (infdata) U = LT_PB_DROP_LOWEST(PM, vmask);
+    const int nu = LT_PB_POPC(PM, U);
     const int numax = wave_max(nu);
     for (int it = 0; it < numax; it++) {
       const bool act = it < nu;
-      const int kq = act ? __builtin_ctzll(U) : 1;  // end vertex of the disturbance (>= 1)
-      if (act) U &= U - 1;
-      const uint64_t below = act ? vmask & ((1ull << kq) - 1) : 1;  // the vertices before kq
-      const int k1 = 63 - __builtin_clzll(below);                     // vertex q-1
-      const uint64_t below2 = below & ~(1ull << k1);
+      const int kq = act ? LT_PB_CTZ(PM, U) : 1;  // end vertex of the disturbance (>= 1)
+      if (act) U = LT_PB_DROP_LOWEST(PM, U);
+      // the vertices before kq (kq below the mask's width; an inactive lane: the placeholder 1,
+      // so that TOP has a bit to find)
+      const PM below = act ? vmask & LT_PB_BELOW(PM, kq) : 1;
+      const int k1 = LT_PB_TOP(PM, below);                 // vertex q-1
+      const PM below2 = below & ~LT_PB_BIT(PM, k1);
       const bool has2 = act && below2 != 0;
-      const int k2 = has2 ? 63 - __builtin_clzll(below2) : 0;         // vertex q-2
-      const uint64_t above = act ? vmask & ~((2ull << kq) - 1) : 0;    // (kq = 63: none)
+      const int k2 = has2 ? LT_PB_TOP(PM, below2) : 0;     // vertex q-2
+      // (kq the mask's last bit: 2 << kq drops out and ABOVE is empty, no vertex above)
+      const PM above = act ? vmask & LT_PB_ABOVE(PM, kq) : 0;
       const bool hasn = above != 0;
-      const int kn = hasn ? __builtin_ctzll(above) : 0;               // vertex q+1
+      const int kn = hasn ? LT_PB_CTZ(PM, above) : 0;      // vertex q+1
       // the reference's eqns (vertices2eqns, utils.py:646-669): e1 of segment q-1 (k1..kq),
       // e2 of segment q-2 (k2..k1), e3 of segment q (kq..kn)
       // the fitted value at vertex q-1 takes e2 (left) or e1 (right), at vertex q e1 (left) or
@@ -1818,16 +1828,16 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
   } else {
     // labels only, in lockstep over the vertex number q: the fitted value at each vertex is all
     // the rules need
-    const int nv = __builtin_popcountll(vmask);
+    const int nv = LT_PB_POPC(PM, vmask);
     const int nvmax = wave_max(nv);
-    uint64_t vrem = vmask;  // vertices from q on: vertex q is its lowest bit
+    PM vrem = vmask;  // vertices from q on: vertex q is its lowest bit
     double pm = 0.0, pb = 0.0;   // eqn of vertex q-1
     for (int q = 0; q < nvmax; q++) {
       const bool act = q < nv;
-      const int ka = act ? __builtin_ctzll(vrem) : 0;
-      if (act) vrem &= vrem - 1;
+      const int ka = act ? LT_PB_CTZ(PM, vrem) : 0;
+      if (act) vrem = LT_PB_DROP_LOWEST(PM, vrem);
       const bool has_next = act && q + 1 < nv;
-      const int kb = has_next ? __builtin_ctzll(vrem) : ka;
+      const int kb = has_next ? LT_PB_CTZ(PM, vrem) : ka;
       double cm = pm, cb = pb;
       // one LAPACK-emulated fit per vertex number for the whole wave (lanes without a next
       // vertex reuse the previous equation, utils.py:662)

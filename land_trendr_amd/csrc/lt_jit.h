@@ -76,9 +76,9 @@ using __hip_internal::true_type;
 #include "lt_jit_embed.inc"
 #endif
 
-constexpr int kNHeaders = 5;
-constexpr const char* kHeaderName[kNHeaders] = {"lt_abi.h", "lt_lapack.h", "lt_pixel.h",
-                                                "lt_fast.h", "lt_kernels_dev.h"};
+constexpr int kNHeaders = 6;
+constexpr const char* kHeaderName[kNHeaders] = {"lt_abi.h",   "lt_bits.h", "lt_lapack.h",
+                                                "lt_pixel.h", "lt_fast.h", "lt_kernels_dev.h"};
 
 inline bool read_file(const std::string& path, std::string& out) {
   FILE* f = fopen(path.c_str(), "rb");

@@ -15,6 +15,7 @@
 #endif
 
 #include "../../include/lt_abi.h"
+#include "lt_bits.h"
 #include "lt_lapack.h"
 
 // The output planes of lt_tile_out as bits (lt_jit.h out_field_mask). A JIT kernel specialised
@@ -140,14 +141,16 @@ struct RuleState1 {
 //     no member of G can win: G restarts from it;
 //   * otherwise it joins G.
 // The winner is always in G, so replaying the exact offers over G alone (RuleState1, in order)
-// gives the reference's winner. G is a mask over the disturbance's end-vertex index.
-struct RuleCands {
-  uint64_t G = 0;
+// gives the reference's winner. G is a mask over the disturbance's end-vertex index: M is the
+// caller's point-mask type (lt_bits.h PointBits; the host callers' RuleCands keeps 64 bits).
+template <class M>
+struct RuleCandsT {
+  M G = 0;
   double lo = -__builtin_inf(), hi = -__builtin_inf();
 
   __host__ __device__ __attribute__((always_inline)) void offer(
       const lt_rule& R, int pre_mode, int32_t d_on, int32_t d_du, double init_lo,
-      double init_hi, double mag_lo, double mag_hi, uint64_t bit, int& status) {
+      double init_hi, double mag_lo, double mag_hi, M bit, int& status) {
     bool match = true, maybe = false;
     if (R.onset_op == LT_Q_EQ) match = match && ((double)d_on == R.onset_val);
     else if (R.onset_op == LT_Q_LE) match = match && !((double)d_on > R.onset_val);
@@ -183,6 +186,7 @@ struct RuleCands {
     if (!maybe) lo = __builtin_fmax(klo, lo);
   }
 };
+typedef RuleCandsT<uint64_t> RuleCands;
 
 // Half-width factor of a closed-form vertex fit against the reference's (emulated dgelsd) one:
 // |fitted value - reference fitted value| <= kFitW * (|slope| * 64 + |intercept| + max|y|) at any
