@@ -30,7 +30,8 @@ namespace {
 constexpr int kBlock = 256;
 
 // one lsq_factor per slot of the x-set table (lt_lapack.h), computed by the device arithmetic
-// that the lookups replace
+// that the lookups replace. xs[64] holds any slot's x-set: m <= 64 (the values themselves reach
+// 63 + 63 = 126: a slot is bounded by its first offset alone)
 __global__ __launch_bounds__(kBlock) void build_xtable_kernel(lt::lsq_xf* __restrict__ xtab) {
   const int idx = blockIdx.x * kBlock + threadIdx.x;
   if (idx >= lt::kXtSize) return;
@@ -39,7 +40,7 @@ __global__ __launch_bounds__(kBlock) void build_xtable_kernel(lt::lsq_xf* __rest
   if (lt::xset_of_key(idx, m, xs))
     lt::lsq_factor(m, [&](int k) { return xs[k]; }, f);
   else
-    f.rc = -4;  // no x-set maps here
+    f.rc = -4;  // xset_key returns this slot for no x-set (m < 5 among the consecutive runs)
   xtab[idx] = f;
 }
 

@@ -906,8 +906,11 @@ __host__ __device__ inline int lstsq_xint(int m, GX X, GY Y, bool need_solution,
 }
 
 // ------------------------------------------------------------------------------------------------
-// Table of lsq_factor results for the x-sets segments usually have (year offsets < 64): m = 2
-// with a gap <= 16, m = 3 with gaps <= 8, m = 4 with gaps <= 4, and m >= 5 consecutive years.
+// Table of lsq_factor results for the x-sets segments usually have, by their first year offset
+// x0 <= 63: m = 2 with a gap <= 16, m = 3 with gaps <= 8, m = 4 with gaps <= 4, and m >= 5
+// consecutive years. Only x0 is bounded: an x-set that starts at or below offset 63 and ends past
+// it (up to 63 + 63 = 126; scenes whose years have gaps, year spans up to 255) has a slot like any
+// other, and every slot xset_key can return is filled (tests/test_span_host.py).
 // Built on the device once per context (lt_abi.hip); lookups that miss factor on the fly. (Slots
 // for 5-8 point x-sets with gaps of 1-2 years were tried: the key's loop, inlined into the
 // year-major output loop, spilled 29 VGPRs of the c5 instance, 986 vs 1190 Mpx/s,
@@ -916,7 +919,7 @@ __host__ __device__ inline int lstsq_xint(int m, GX X, GY Y, bool need_solution,
 constexpr int kXtM2 = 0, kXtM3 = 64 * 16, kXtM4 = kXtM3 + 64 * 64, kXtCons = kXtM4 + 64 * 64,
               kXtSize = kXtCons + 64 * 64;
 
-// table slot of the x-set X(0) < ... < X(m-1) (all < 64), or -1
+// table slot of the x-set X(0) < ... < X(m-1) (X(0) <= 63, the others as the gaps allow), or -1
 template <class GX>
 __host__ __device__ inline int xset_key(int m, GX X) {
   const int x0 = X(0);
@@ -940,7 +943,8 @@ __host__ __device__ inline int xset_key(int m, GX X) {
   return -1;
 }
 
-// the x-set of table slot idx: m and xs[0..m-1]; false for a slot no x-set maps to
+// the x-set of table slot idx: m and xs[0..m-1] (m <= 64, xs[m-1] <= 126); false for a slot no
+// x-set maps to (the m < 5 slots of the consecutive-years part)
 __host__ __device__ inline bool xset_of_key(int idx, int& m, int* xs) {
   int d[3] = {1, 1, 1};
   if (idx < kXtM3) {
@@ -969,7 +973,7 @@ __host__ __device__ inline bool xset_of_key(int idx, int& m, int* xs) {
     return false;
   }
   for (int k = 1; k < m; k++) xs[k] = xs[k - 1] + (m <= 4 ? d[k - 1] : 1);
-  return xs[m - 1] <= 63;
+  return true;
 }
 
 }  // namespace lt
