@@ -85,6 +85,28 @@
 #else
 #define LT_DP_SEED_SPEC 0
 #endif
+// The one-rule labels-only kernels specialised for a configuration (c2, c4: no per-year plane),
+// analyze stage: the scope of the switch below. (The per-year kernels, the modules of several
+// rules, the resolve stage and the precompiled instances keep the code they had.)
+#if defined(LT_SPEC_NRULES) && defined(LT_SPEC_YEAR_OUT)
+#if LT_SPEC_NRULES == 1 && LT_SPEC_YEAR_OUT == 0
+#define LT_LABELS1_SPEC 1
+#endif
+#endif
+#ifndef LT_LABELS1_SPEC
+#define LT_LABELS1_SPEC 0
+#endif
+// the certified labels path's pass A trimmed (LT_FIT_TRIM, default on: the vertex loop unrolled by
+// two over alternating state, 1/m from an LDS table, an integer |y| maximum, the vertex's point
+// taken from its segment's sums; 0: the loop as it was)
+#ifndef LT_FIT_TRIM
+#define LT_FIT_TRIM 1
+#endif
+#if LT_FIT_TRIM && LT_LABELS1_SPEC
+#define LT_FIT_TRIM_SPEC 1
+#else
+#define LT_FIT_TRIM_SPEC 0
+#endif
 
 namespace lt {
 
@@ -95,6 +117,16 @@ namespace lt {
 __device__ inline int dmul24(int m, int sxx, int sx) {
   return (int)(__umul24((unsigned)m, (unsigned)sxx) - __umul24((unsigned)sx, (unsigned)sx));
 }
+
+// T if B, else F (std::conditional, which hiprtc's own headers do not bring)
+template <bool B, class T, class F>
+struct PickType {
+  typedef T type;
+};
+template <class T, class F>
+struct PickType<false, T, F> {
+  typedef F type;
+};
 
 // max over the 64 lanes of a wave (every lane must call it). readfirstlane makes the result an
 // SGPR value, so loops bounded by it are wave-uniform to the compiler: scalar branches instead
@@ -157,6 +189,16 @@ __device__ inline int lsq_fit_lockstep(bool act, int m, GX X, GY Y,
   return rc;
 }
 
+// Reciprocal table of the analyze stage (AGLDS false), each wave's own, filled at kernel entry
+// beside the year table: 1/m of a segment's point count m = 1..MAXY (LT_FIT_TRIM_SPEC). An empty
+// base where the kernel does not use it: the other kernels' LDS layout is what it was.
+template <int MAXY, bool ON>
+struct RcpMTab {};
+template <int MAXY>
+struct RcpMTab<MAXY, true> {
+  double rcp_m[MAXY];  // [m - 1]
+};
+
 // VT: storage type of the series. The analyze stage stores int16 (an int16 index raster), binary32
 // (other index types: pixels whose values are not exact in binary32 are sent to the resolve stage)
 // or binary64 (binary64 values, up to 4 rules); the resolve stage the same, or binary64.
@@ -164,7 +206,7 @@ __device__ inline int lsq_fit_lockstep(bool act, int m, GX X, GY Y,
 // registers / private memory) or, when false, in the lane's registers / private memory (analyze
 // stage, the lazy DP: 2 KB less LDS per wave, 15 instead of 12 resident waves per CU)
 template <int MAXY, class VT, bool AGLDS>
-struct WaveLds {
+struct WaveLds : RcpMTab<MAXY, LT_FIT_TRIM_SPEC != 0 && !AGLDS> {
   VT ys[MAXY][64];       // present values (t), compacted in place to non-spike (k)
   uint8_t xn[MAXY][64];  // year offset of non-spike point k
   uint8_t ag[AGLDS ? MAXY : 1][64];  // DP argmin of column k (AGLDS only)
@@ -213,6 +255,16 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
   int status = LT_ST_OK;
   static_assert(LT_MAX_YEARS == 64, "one year-table word per lane");
   if (lane < Y) L.year[lane] = S.year[lane];
+  // the reciprocal table (WaveLds), each entry by the sequence its reader replaced: v_rcp_f64 and
+  // one Newton step
+  constexpr bool kFitTrim = LT_FIT_TRIM_SPEC != 0 && RMAX == 1 && !EXACT;
+  if constexpr (kFitTrim) {
+    if (lane < MAXY) {
+      const double md = (double)(lane + 1);
+      double rm = __builtin_amdgcn_rcp(md);
+      L.rcp_m[lane] = __builtin_fma(rm, __builtin_fma(-md, rm, 1.0), rm);
+    }
+  }
 #ifdef LT_DEBUG_LDS_POISON
   // debugging (LT_JIT_DEFINES=LT_DEBUG_LDS_POISON=v): the lane's series slots filled with a junk
   // pattern first, so a read of a slot this pixel did not write shows up as a changed result
@@ -1661,6 +1713,153 @@ __device__ inline int analyze_fast(const DevScene& S_launch, const lt_params& P,
       Sxy = __builtin_fma((double)xi, yi, Sxy);
       ymx = __builtin_fmax(ymx, __builtin_fabs(yi));
     };
+    if constexpr (kFitTrim) {
+      // LT_FIT_TRIM: the same values, each from fewer instructions.
+      //  * The state a vertex hands to the next (eqn, error scale, fitted value's interval, year)
+      //    lives in two register sets; vertex q reads the set vertex q-1 wrote and writes the
+      //    other, and the loop is unrolled by two, so nothing is copied at the end of an
+      //    iteration (as the DP's column() rotates its window). A lane's last vertex, which
+      //    reuses the previous eqn (utils.py:662), is priced from the set it reads: it writes no
+      //    eqn, and nothing of that lane is read after it.
+      //  * The vertex's own point is its segment's first: x and the raw value come from the sums'
+      //    loads. Only a lane's last vertex, without a next segment, loads its x.
+      //  * 1/m is read from the wave's table (WaveLds rcp_m: the bits of the reciprocal and
+      //    Newton step it replaces); 1/D keeps its reciprocal.
+      //  * max |y| of an int16 series is an integer maximum, converted once (exact either way).
+      using YMax = typename PickType<kIntSeries, int, double>::type;
+      auto add_pt2 = [&](int k, int& Sx, int& Sxx, double& Sy, double& Sxy, YMax& ymx, int& xo,
+                         double& yo) __attribute__((always_inline)) {
+        const int xi = L.xn[k][lane];
+        const VT yv = L.ys[k][lane];
+        const double yi = (double)yv;
+        Sx += xi;
+        Sxx += xi * xi;
+        Sy += yi;
+        Sxy = __builtin_fma((double)xi, yi, Sxy);
+        if constexpr (kIntSeries) {
+          const int a = (int)yv;
+          const int aa = a < 0 ? -a : a;
+          ymx = aa > ymx ? aa : ymx;
+        } else {
+          ymx = __builtin_fmax(ymx, __builtin_fabs(yi));
+        }
+        xo = xi;
+        yo = yi;
+      };
+      // vertex q: p* the state of vertex q-1 (read), c* that of vertex q (written)
+      auto vertex = [&](const int q, const double& pm, const double& pb, const double& psc,
+                        const double& pf, const double& pw, const int32_t& py, double& cm,
+                        double& cb, double& csc, double& cf, double& cw, int32_t& cy)
+                        __attribute__((always_inline)) {
+        const bool act = q < nv;
+        const int ka = act ? LT_PB_CTZ(PM, vrem) : 0;
+        if (act) vrem = LT_PB_DROP_LOWEST(PM, vrem);
+        const bool has_next = act && q + 1 < nv;
+        if (__ballot(has_next)) {
+          const int kb = has_next ? LT_PB_CTZ(PM, vrem) : ka;
+          const int m = kb - ka + 1;
+          // (the sums, the vertex's x and raw value: of the lanes with a next vertex, which alone
+          // read them, so nothing is set for the others)
+          int Sx, Sxx, xa, xu;
+          double Sy, Sxy, ya, yu;
+          YMax ymx;
+          if (has_next) {
+            if constexpr (kIntSeries) {
+              // the first point assigned, not added to zeros: 0.0 + y is y for an integer y (no
+              // -0.0), and the fma keeps its zero addend
+              xa = L.xn[ka][lane];
+              const int a = (int)L.ys[ka][lane];
+              ya = (double)a;
+              Sx = xa;
+              Sxx = xa * xa;
+              Sy = ya;
+              Sxy = __builtin_fma((double)xa, ya, 0.0);
+              ymx = a < 0 ? -a : a;
+            } else {
+              Sx = Sxx = 0;
+              Sy = Sxy = 0.0;
+              ymx = 0;
+              add_pt2(ka, Sx, Sxx, Sy, Sxy, ymx, xa, ya);
+            }
+            add_pt2(ka + 1, Sx, Sxx, Sy, Sxy, ymx, xu, yu);
+            if (m >= 3) add_pt2(ka + 2, Sx, Sxx, Sy, Sxy, ymx, xu, yu);
+            if (m >= 4) add_pt2(ka + 3, Sx, Sxx, Sy, Sxy, ymx, xu, yu);
+          }
+          const bool longer = has_next && m > 4;
+          if (__ballot(longer)) {
+            const int mmax = wave_max(longer ? m : 0);
+            for (int k = 4; k < mmax; k++)
+              if (k < m) add_pt2(ka + k, Sx, Sxx, Sy, Sxy, ymx, xu, yu);
+          }
+          if (has_next) {
+            const double md = (double)m;
+            // m <= 64, Sxx <= 64 * 255^2 < 2^24, Sx <= 64 * 255 < 2^14: dmul24's factors
+            const double D = (double)dmul24(m, Sxx, Sx);  // > 0: distinct x
+            const double N1 = __builtin_fma(md, Sxy, -((double)Sx * Sy));
+            double r = __builtin_amdgcn_rcp(D);
+            r = __builtin_fma(r, __builtin_fma(-D, r, 1.0), r);
+            const double rm = L.rcp_m[m - 1];
+            cm = N1 * r;
+            cb = __builtin_fma(-cm, (double)Sx, Sy) * rm;
+            csc = __builtin_fma(__builtin_fabs(cm), 64.0, __builtin_fabs(cb)) + (double)ymx;
+            // a segment reaching past year offset 63: kFitWide (lt_pixel.h fit_width)
+            csc *= fit_width_factor(L.xn[kb][lane]);
+            // the fitted value at vertex q (eqns2fitted_points: the closer of the left and right
+            // eqn)
+            const double x = (double)xa;
+            const double fr = (cm * x) + cb, wr = kFitW * csc;
+            double f = fr, w = wr;
+            if (q > 0) {
+              const double fl = (pm * x) + pb, wl = kFitW * psc;
+              const double dl = __builtin_fabs(fl - ya), dr = __builtin_fabs(fr - ya);
+              const double slack = wl + wr + 0x1p-50 * (dl + dr);
+              const bool left = dl + slack <= dr;             // certainly the left eqn
+              const bool right = !left && dr + slack < dl;    // certainly the right eqn
+              // (selects and one branch for the hull: the three-way branch merged its values
+              // through register copies)
+              f = left ? fl : fr;
+              w = left ? wl : wr;
+              CL |= left ? LT_PB_BIT(PM, ka) : (PM)0;
+              CR |= right ? LT_PB_BIT(PM, ka) : (PM)0;
+              if (!left && !right) {  // either: the hull of both intervals
+                const double lo = __builtin_fmin(fl - wl, fr - wr),
+                             hi = __builtin_fmax(fl + wl, fr + wr);
+                f = 0.5 * (lo + hi);
+                w = 0.5 * (hi - lo) + 0x1p-50 * (__builtin_fabs(lo) + __builtin_fabs(hi));
+              }
+            }
+            cf = f;
+            cw = w;
+            cy = y0 + xa;
+          }
+        }
+        const bool last = act && !has_next;
+        if (__ballot(last)) {
+          if (last) {  // the previous eqn at the lane's last vertex (all zero when it is its only)
+            const int xl = L.xn[ka][lane];
+            cf = (pm * (double)xl) + pb;
+            cw = kFitW * psc;
+            cy = y0 + xl;
+          }
+        }
+        if (act && q > 0) {  // the disturbance from vertex q-1 to vertex q (classes.py:156-176)
+          const double mag = pf - cf;
+          const double wm = (pw + cw) + 0x1p-50 * (__builtin_fabs(pf) + __builtin_fabs(cf));
+#pragma unroll
+          for (int r = 0; r < RMAX; r++)
+            if (r < LT_NRULES)
+              cand[r].offer(LT_RULE(r), LT_PRE_MODE, py, cy - py, pf - pw, pf + pw, mag - wm,
+                            mag + wm, LT_PB_BIT(PM, ka), status);
+        }
+      };
+      double bm = 0.0, bb = 0.0, bsc = 0.0, bf = 0.0, bw = 0.0;  // the second set (am.. the first)
+      int32_t by = 0;
+      for (int q = 0; q < nvmax; q += 2) {
+        vertex(q, bm, bb, bsc, bf, bw, by, am, ab, asc, fprev, wprev, yprev);
+        if (q + 1 >= nvmax) break;
+        vertex(q + 1, am, ab, asc, fprev, wprev, yprev, bm, bb, bsc, bf, bw, by);
+      }
+    } else
     for (int q = 0; q < nvmax; q++) {
       const bool act = q < nv;
       const int ka = act ? LT_PB_CTZ(PM, vrem) : 0;
