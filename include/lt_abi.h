@@ -38,6 +38,7 @@ extern "C" {
 #define LT_MAX_RULES 16
 #define LT_NODATA (-99)   /* settings.py:16 */
 #define LT_MAX_TILE_PIX (1LL << 28) /* pixels per analyzed tile (lt_tile_in.n_pix)           */
+#define LT_MAX_ZONES 65536          /* zones of a zonal table (lt_zonal_stats)                */
 
 /* Per-pixel status bits (lt_tile_out.status). Non-zero = the reference raises for this pixel. */
 enum {
@@ -553,6 +554,28 @@ int lt_change_maps(lt_ctx* ctx, const lt_change_in* in, int n_maps, const lt_cha
  * n_pix > LT_MAX_TILE_PIX; LT_OK at once for n_pix == 0. */
 int lt_label_counts(lt_ctx* ctx, const uint8_t* matched, const int32_t* key, int64_t n_pix,
                     int32_t key_lo, int32_t n_bins, uint64_t* counts, void* stream);
+/* A label plane summed per zone and key (area, mean duration and mean magnitude per zone and onset
+ * year; land_trendr_amd/csrc/lt_zonal.h). All planes are DEVICE pointers with unit stride over
+ * n_pix pixels: matched, zone (a dense zone index), key, duration (or NULL), value (or NULL).
+ * `table` (DEVICE) is [n_zones + 1][n_bins + 1][4] 64-bit words and is added to, so the caller
+ * zeroes it. For every pixel with matched != 0: the row is zone if 0 <= zone < n_zones, else
+ * n_zones; the column is key - key_lo (in 64 bits) if it lies in [0, n_bins), else n_bins; word 0
+ * += 1; word 1 += duration (sign-extended) with a duration plane; and with a value plane and
+ * v = value[p] not NaN, word 2 += (int64) rint(clamp(v, -2^30, 2^30) * 16.0) (round half to even;
+ * +-inf clamp; |addend| <= 2^34) and word 3 += 1, so a mean is word 2 / 16 / word 3. Every word is
+ * a two's-complement sum made with unsigned 64-bit adds: the result is a function of the input
+ * alone, and equal on every path. No word can wrap within one call on a zeroed table (n_pix <=
+ * 2^28); a caller that accumulates several calls owns that bound. path: 0 chooses, 1 forces the
+ * block-private LDS table (LT_ERR_ARG unless (n_zones + 1) * (n_bins + 1) <= 1024), 2 the
+ * wave-combined global adds. Asynchronous on `stream`; reads nothing back. LT_ERR_ARG, with
+ * nothing launched, for a null matched / zone / key / table, a negative n_pix, n_bins outside
+ * [1, 256], n_zones outside [1, LT_MAX_ZONES] and a path outside [0, 2]; LT_ERR_LIMIT for
+ * n_pix > LT_MAX_TILE_PIX; LT_OK at once for n_pix == 0, before any other argument is looked at
+ * (as lt_label_counts: with no pixel, null pointers and sizes outside their ranges are not
+ * errors; every check but the negative n_pix applies to n_pix > 0 only). */
+int lt_zonal_stats(lt_ctx* ctx, const uint8_t* matched, const int32_t* zone, const int32_t* key,
+                   const int32_t* duration, const double* value, int64_t n_pix, int32_t key_lo,
+                   int32_t n_bins, int32_t n_zones, int32_t path, uint64_t* table, void* stream);
 
 /* Output raster assembly: n_jobs rasters (lt_raster_job), asynchronous on `stream`: a fill of
  * every raster pixel with NODATA's converted value, then the selected grid points scattered in

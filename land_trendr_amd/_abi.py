@@ -262,6 +262,11 @@ class LtSieveOut(ctypes.Structure):
                 ('workspace_bytes', ctypes.c_int64)]
 
 
+LT_MAX_ZONES = 65536
+# lt_zonal_stats' path argument
+LT_ZONAL_AUTO, LT_ZONAL_LDS, LT_ZONAL_WAVE = 0, 1, 2
+LT_ZONAL_LDS_CELLS = 1024  # path 1 needs (n_zones + 1) * (n_bins + 1) <= this
+
 LT_MAX_CHANGE_MAPS = 8
 LT_CM_LOSS, LT_CM_GAIN = 0, 1
 (LT_CS_GREATEST, LT_CS_LEAST, LT_CS_NEWEST, LT_CS_OLDEST, LT_CS_LONGEST, LT_CS_SHORTEST,
@@ -345,7 +350,7 @@ EXPORTS = ['lt_abi_version', 'lt_ctx_create', 'lt_ctx_destroy', 'lt_last_error',
            'lt_tiff_encode_strips_dev', 'lt_grid_sample_dev', 'lt_mask_codegen',
            'lt_mask_compile', 'lt_mask_apply', 'lt_tiff_decode_chunks_dev', 'lt_ftv_tile',
            'lt_vertex_table', 'lt_sieve_labels', 'lt_sieve_workspace_bytes', 'lt_change_maps',
-           'lt_label_counts']
+           'lt_label_counts', 'lt_zonal_stats']
 
 LT_JIT_SYNC, LT_JIT_ASYNC = 0, 1
 LT_JIT_SRC_SPEC, LT_JIT_SRC_SCENE, LT_JIT_SRC_FIELDS = 1, 2, 4
@@ -403,6 +408,8 @@ def load_lib(path=None):
                                    ctypes.POINTER(LtChangeRule), ctypes.POINTER(LtChangeOut), vp]
     lib.lt_label_counts.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                     vp, vp]
+    lib.lt_zonal_stats.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int32,
+                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp]
     lib.lt_sieve_labels.argtypes = [vp, ctypes.POINTER(LtSieveIn), ctypes.POINTER(LtSieveOut), vp]
     lib.lt_sieve_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
     lib.lt_sieve_workspace_bytes.restype = ctypes.c_int64

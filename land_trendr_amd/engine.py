@@ -534,6 +534,65 @@ class Engine:
         self._check(rc, 'lt_label_counts')
         return out
 
+    # --- zonal table: a label plane summed per zone and key (lt_zonal_stats, lt_zonal.hip) ---
+    def zonal_stats(self, matched, zone, key, key_lo, n_bins, n_zones, duration=None, value=None,
+                    out=None, _path=0):
+        """A label plane summed per zone and key: matched uint8 [P], zone int32 [P] (a dense zone
+        index), key int32 [P] and, optionally, duration int32 [P] and value float64 [P], device
+        tensors with unit stride. Returns an int64 [n_zones + 1, n_bins + 1, 4] device tensor: for
+        the pixels with matched != 0, row zone (the last row for an index outside [0, n_zones)),
+        column key - key_lo (the last column for a key outside [key_lo, key_lo + n_bins)), the
+        four words hold the pixel count, the sum of duration, the sum of rint(clamp(value, -2^30,
+        2^30) * 16) over the values that are not NaN, and the count of those (a mean magnitude is
+        word 2 / 16 / word 3). n_bins is in [1, 256], n_zones in [1, 65536]. Without duration /
+        value their words are left as they are. out: an int64 [n_zones + 1, n_bins + 1, 4] tensor
+        the sums are added to (the caller zeroes it). Integer sums: the table is a function of
+        the input alone. Runs on the current stream and does not synchronise."""
+        for name, v in (('key_lo', key_lo), ('n_bins', n_bins), ('n_zones', n_zones),
+                        ('_path', _path)):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise LtError('%s must be an integer' % name)
+        if not 1 <= n_bins <= 256:
+            raise LtError('n_bins must be in [1, 256]')
+        if not 1 <= n_zones <= _abi.LT_MAX_ZONES:
+            raise LtError('n_zones must be in [1, %d]' % _abi.LT_MAX_ZONES)
+        if not -2 ** 31 <= key_lo <= 2 ** 31 - 1:
+            raise LtError('key_lo must be an int32')
+        if _path not in (0, 1, 2):
+            raise LtError('_path must be 0, 1 or 2')
+        if (not isinstance(matched, torch.Tensor) or matched.dtype != torch.uint8 or
+                matched.device != self.device or matched.dim() != 1 or
+                (matched.numel() > 1 and matched.stride(0) != 1)):
+            raise LtError('matched must be a uint8 [P] tensor on %s with unit stride'
+                          % self.device)
+        P = matched.numel()
+        for name, t, dt, need in (('zone', zone, torch.int32, True), ('key', key, torch.int32, True),
+                                  ('duration', duration, torch.int32, False),
+                                  ('value', value, torch.float64, False)):
+            if t is None and not need:
+                continue
+            if (not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != self.device or
+                    t.dim() != 1 or t.numel() != P or (P > 1 and t.stride(0) != 1)):
+                raise LtError('%s must be a [%d] tensor of %s on %s with unit stride'
+                              % (name, P, str(dt).replace('torch.', ''), self.device))
+        shape = (n_zones + 1, n_bins + 1, 4)
+        if out is None:
+            out = torch.zeros(shape, dtype=torch.int64, device=self.device)
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or
+                out.device != self.device or tuple(out.shape) != shape or not out.is_contiguous()):
+            raise LtError('out must be a contiguous int64 [n_zones + 1, n_bins + 1, 4] tensor on %s'
+                          % self.device)
+        if P == 0:
+            return out
+        st = torch.cuda.current_stream(self.device)
+        rc = self.lib.lt_zonal_stats(
+            self.ctx, matched.data_ptr(), zone.data_ptr(), key.data_ptr(),
+            duration.data_ptr() if duration is not None else None,
+            value.data_ptr() if value is not None else None, P, key_lo, n_bins, n_zones, _path,
+            out.data_ptr(), ctypes.c_void_p(st.cuda_stream))
+        self._check(rc, 'lt_zonal_stats')
+        return out
+
     # --- MMU sieve: patches of a label plane below a minimum size (lt_sieve_labels) ---
     def sieve(self, matched, key, shape, min_pixels, connectivity=8, apply=True, out=None,
               _phases=None):

@@ -45,6 +45,11 @@ that has an mmu (its own, else the top-level one), counts the pixels per onset y
 (LocalJob.change_stats) and writes 'change/<name>-onset_year', '-duration', '-magnitude', '-preval',
 '-rate', '-dsnr' for every map with a match, and 'change/rmse'.
 
+With settings.json zonal_stats (a zone raster of integer ids; settings.check_zonal_stats) output()
+sums every label rule's and every change map's published planes per zone and onset year on the GPU
+(one rank; Engine.zonal_stats) into LocalJob.zonal_stats and 'output/tables/zonal-<name>.csv':
+pixels, area, mean magnitude and mean duration per cell. No raster is written or changed.
+
 Multi-rank jobs: rank 0 alone extracts the compressed rasters and writes the grid, then every rank
 reads them (a barrier between), so no rank sees a partial extraction or a truncated grid.
 
@@ -72,6 +77,24 @@ IN_SETTINGS = '%s/input/settings.json'
 IN_RASTS = '%s/input/rasters/'
 OUT_GRID = '%s/output/pix_grid.csv'
 OUT_RASTS = '%s/output/rasters/'
+
+
+def zonal_csv(res):
+    """One entry of LocalJob.zonal_stats as the text of its 'tables/zonal-<name>.csv': a header,
+    then one line per (zone id, onset year) cell with a pixel in it, zones ascending (the row
+    outside every zone last, its id 'outside'), years ascending (the column of the onset years
+    outside the scene's last, its year 'other'): zone,year,pixels,area,mean_magnitude,
+    mean_duration. The numbers are Python's shortest round-trip forms; a cell without a magnitude
+    that is not NaN has an empty mean_magnitude."""
+    t = res['table']
+    rows = [str(int(z)) for z in res['zone_ids']] + ['outside']
+    cols = [str(int(y)) for y in res['years']] + ['other']
+    lines = ['zone,year,pixels,area,mean_magnitude,mean_duration']
+    for r, c in zip(*np.nonzero(t[..., 0])):
+        n, dur, q, nv = (int(v) for v in t[r, c])
+        lines.append('%s,%s,%d,%r,%s,%r' % (rows[r], cols[c], n, float(n * res['pixel_area']),
+                                            repr(q / 16.0 / nv) if nv else '', dur / n))
+    return '\n'.join(lines) + '\n'
 
 
 class _LazyBands(dict):
@@ -222,6 +245,14 @@ class LocalJob:
         # 'by_year': {onset year: pixels after the sieve}}} once output() ran; None without the key
         self.change_stats = None
         self.change_s = 0.0  # seconds of the change maps' share of analyze() and output()
+        # settings.json zonal_stats: {rule or map name: {'table' int64 [Z + 1, B + 1, 4], 'pixels',
+        # 'area', 'mean_magnitude', 'mean_duration' [Z + 1, B + 1], 'zone_ids' [Z], 'years' [B],
+        # 'pixel_area'}} once output() ran (the last row: outside every zone; the last column:
+        # an onset year outside the scene's); None without the key
+        self.zonal_stats = None
+        self.zonal_files = None  # {name: path of 'tables/zonal-<name>.csv'}
+        self.zonal_s = 0.0  # seconds of the zonal tables in output(), the zone raster included
+        self._zones = None  # (zone index of each internal pixel int32 [P], zone ids int64 [Z])
         if os.path.exists(self.settings_path):  # what the job cannot do is said at construction
             try:
                 with open(self.settings_path) as f:
@@ -233,6 +264,17 @@ class LocalJob:
                 self._check_vertex(peek)
                 self._check_mmu(peek)
                 self._check_change_maps(peek)
+                self._check_zonal(peek)
+
+    def _check_zonal(self, settings):
+        """settings.json zonal_stats: validated (settings.check_zonal_stats), and supported by a
+        job of one rank; ValueError otherwise."""
+        from .settings import check_zonal_stats
+        if 'zonal_stats' not in check_zonal_stats(settings):
+            return
+        if self._dist()[1] > 1:
+            raise ValueError('zonal_stats is supported on one rank only (world size %d): the '
+                             'zonal tables are not distributed' % self._dist()[1])
 
     def _check_ftv(self, settings):
         """settings.json ftv_eqns: validated (settings.check_ftv_eqns), and supported by a job of
@@ -362,6 +404,7 @@ class LocalJob:
         self._check_vertex(self.settings)
         self._check_mmu(self.settings)
         self._check_change_maps(self.settings)
+        self._check_zonal(self.settings)
         return self.rast_fns
 
     def _internal_order(self):
@@ -1105,6 +1148,123 @@ class LocalJob:
         self._change_live = [int(c[1, m].sum()) > 0 for m in range(M)]
         self.change_s += time.perf_counter() - t0
 
+    def _zone_index(self, opt):
+        """settings.json zonal_stats, once per job: the zone raster sampled at the grid points on
+        the host as every other raster is (GeoTiff.read and grid_offsets: pt2val's truncation, but
+        not its wrap of a negative offset). -> (zone index of each internal pixel, int32 [P]; the
+        zone ids, int64 [Z] ascending): index k is the k-th smallest id; a grid point off the
+        raster, on its GDAL_NODATA value or on an ignored id has index -1."""
+        if self._zones is not None:
+            return self._zones
+        fn = opt['zones']
+        if not os.path.isabs(fn):
+            fn = os.path.join(self.root, self.job, 'input', fn)
+        if not os.path.exists(fn):
+            raise ValueError('zonal_stats: no zone raster %s' % fn)
+        zt = GeoTiff(fn)
+        if zt.dtype.kind not in 'iu':
+            raise ValueError('zonal_stats: the zone raster %s holds %s samples; integer zone ids '
+                             'are required' % (fn, zt.dtype.newbyteorder('=')))
+        if opt['band'] > zt.bands:
+            raise ValueError('zonal_stats: band %d of a zone raster with %d band(s)'
+                             % (opt['band'], zt.bands))
+        lng, lat = self.grid_xy
+        zgt = zt.geotransform()
+        lng, lat = np.asarray(lng), np.asarray(lat)
+        at, ok = grid_offsets(zgt, (zt.height, zt.width), lng, lat)
+        # a zone is a place: a point whose offset truncates below zero is off the raster (pt2val's
+        # numpy indexing would wrap it to the far side; the analysis rasters keep that); an offset
+        # in (-1, 0) truncates to zero, as pt2val's does, and reads the first row or column
+        ok = ok & (np.trunc((lng - zgt[0]) * 1.0 / zgt[1]) >= 0) & \
+            (np.trunc((lat - zgt[3]) * 1.0 / zgt[5]) >= 0)
+        band = zt.read()[opt['band'] - 1].reshape(-1)
+        ids = band[at]
+        if ids.dtype.kind == 'u' and ids.dtype.itemsize == 8:
+            if ids.max(initial=0) >= 2 ** 63:
+                raise ValueError('zonal_stats: zone ids of 2^63 and above are not supported')
+        ids = ids.astype(np.int64)
+        live = np.asarray(ok, bool).copy()
+        drop = list(opt['ignore'])
+        if zt.nodata is not None and float(zt.nodata).is_integer():
+            drop.append(int(zt.nodata))
+        if drop:
+            live &= ~np.isin(ids, np.array(drop, np.int64))
+        zone_ids, dense = np.unique(ids[live], return_inverse=True)
+        if len(zone_ids) > _abi.LT_MAX_ZONES:
+            raise ValueError('zonal_stats: %d distinct zone ids, more than LT_MAX_ZONES (%d)'
+                             % (len(zone_ids), _abi.LT_MAX_ZONES))
+        index = np.full(len(ids), -1, np.int32)
+        index[live] = dense.astype(np.int32)
+        self._zones = (index, zone_ids.astype(np.int64))
+        return self._zones
+
+    def _zonal_output(self, tmpl):
+        """settings.json zonal_stats, after the sieve and the change maps' output pass and before
+        any raster is assembled: every label rule's and every change map's published planes
+        (matched, onset_year, duration, magnitude: EMPTY and rejected pixels cleared, the MMU
+        applied) summed per zone and onset year on their device (Engine.zonal_stats), all tables
+        read back in one copy, into self.zonal_stats and 'output/tables/zonal-<name>.csv'. No
+        raster is written or changed."""
+        from .settings import zonal_stats_options
+        opt = zonal_stats_options(self.settings)
+        self.zonal_stats = self.zonal_files = None
+        if opt is None:
+            return
+        import torch
+        eng = self.engine
+        if not hasattr(eng, 'zonal_stats'):
+            raise RuntimeError('zonal_stats needs the HIP engine (no CPU path exists)')
+        t0 = time.perf_counter()
+        index, zone_ids = self._zone_index(opt)
+        Z = len(zone_ids)
+        nz = max(Z, 1)  # (no zone at all: one row that stays empty, dropped below)
+        years = [int(y) for y in self.scene.years]
+        lo = min(years)
+        n_bins = min(max(years) - lo + 1, 256)
+        jobs = []  # (name, the four plane rows)
+        if 'labels' in opt['of']:
+            dp = self.dev_planes
+            jobs += [(rule.name, [dp[f][r] for f in ('matched', 'onset_year', 'duration',
+                                                      'magnitude')])
+                     for r, rule in enumerate(self.rules)]
+        if 'change_maps' in opt['of'] and self.change_planes is not None:
+            cm = self.change_planes
+            jobs += [(o['name'], [cm[f][m] for f in ('matched', 'onset_year', 'duration',
+                                                      'magnitude')])
+                     for m, o in enumerate(self._change_opts)]
+        gt = tmpl.geotransform()
+        pixel_area = abs(gt[1] * gt[5])
+        self.zonal_stats, self.zonal_files = {}, {}
+        if jobs:
+            dev = jobs[0][1][0].device
+            zone = torch.from_numpy(index).to(dev)
+            tables = torch.zeros((len(jobs), nz + 1, n_bins + 1, 4), dtype=torch.int64, device=dev)
+            for i, (_, (mt, on, du, mg)) in enumerate(jobs):
+                eng.zonal_stats(mt, zone.to(mt.device), on, lo, n_bins, nz, duration=du, value=mg,
+                                out=tables[i])
+            host = tables.cpu().numpy()  # the one read-back
+            keep_rows = list(range(Z)) + [nz]
+            tdir = os.path.join(self.root, self.job, 'output', 'tables')
+            os.makedirs(tdir, exist_ok=True)
+            bin_years = np.arange(lo, lo + n_bins, dtype=np.int32)
+            for (name, _), full in zip(jobs, host):
+                t = np.ascontiguousarray(full[keep_rows])
+                with np.errstate(invalid='ignore', divide='ignore'):
+                    res = {'table': t, 'pixels': t[..., 0].copy(),
+                           'area': t[..., 0] * pixel_area,
+                           'mean_magnitude': np.where(t[..., 3] > 0,
+                                                      t[..., 2] / 16.0 / t[..., 3], np.nan),
+                           'mean_duration': np.where(t[..., 0] > 0,
+                                                     t[..., 1] / t[..., 0].astype(np.float64),
+                                                     np.nan),
+                           'zone_ids': zone_ids, 'years': bin_years, 'pixel_area': pixel_area}
+                self.zonal_stats[name] = res
+                path = os.path.join(tdir, 'zonal-%s.csv' % name)
+                with open(path, 'w', newline='') as fh:
+                    fh.write(zonal_csv(res))
+                self.zonal_files[name] = path
+        self.zonal_s = time.perf_counter() - t0
+
     # 4. output_reducer
     def output(self):
         """Every output key's raster, written as LZW GeoTIFF with the template's georeferencing.
@@ -1137,6 +1297,7 @@ class LocalJob:
         self._host = None
         self._sieve(rows, cols)
         self._change_output(rows, cols)
+        self._zonal_output(tmpl)
         names = [d.strftime('%Y-%m-%d') for d in self.scene.dates]
         cuda = torch.device(self.engine.device).type == 'cuda'
         distinct = self._raster_hw is not None or np.bincount(dest, minlength=rows * cols).max() <= 1

@@ -228,14 +228,86 @@ def change_map_options(settings):
     return out
 
 
+_ZONAL_KEYS = ('zones', 'band', 'ignore', 'of')
+ZONAL_OF = ('labels', 'change_maps')
+
+
+def check_zonal_stats(settings):
+    """settings['zonal_stats'], if present: the per-zone, per-onset-year tables of the label rules
+    and the change maps. A string is short for {"zones": that string}; the long form is
+      zones   a GeoTIFF of integer zone ids: a file name under <root>/<job>/input/, or an absolute
+              path (required, non-empty)
+      band    the band that holds the ids, an integer >= 1 (default 1)
+      ignore  a list of integer zone ids to leave out (default none; the raster's own GDAL_NODATA
+              value is always left out)
+      of      a non-empty list out of "labels" and "change_maps", no entry twice: whose tables are
+              made (default: both where present); "change_maps" needs the change_maps key
+    Anything else (a number, a bool, an empty name, an unknown sub-key, a float id, a band below 1)
+    is a ValueError that names zonal_stats; an absent key changes nothing."""
+    if 'zonal_stats' not in settings:
+        return settings
+    v = settings['zonal_stats']
+
+    def bad(msg):
+        return ValueError('zonal_stats: ' + msg)
+    if isinstance(v, str):
+        v = {'zones': v}
+    if not isinstance(v, dict):
+        raise bad('must be a file name or an object, not %r' % (v,))
+    unknown = sorted(set(v) - set(_ZONAL_KEYS), key=str)
+    if unknown:
+        raise bad('unknown keys %r (known: %s)' % (unknown, ', '.join(_ZONAL_KEYS)))
+    z = v.get('zones')
+    if not isinstance(z, str) or not z.strip():
+        raise bad('zones must be a file name, not %r' % (z,))
+    b = v.get('band', 1)
+    if not _is_int(b) or not 1 <= b <= 65535:
+        raise bad('band must be an integer in [1, 65535], not %r' % (b,))
+    ig = v.get('ignore', [])
+    if not isinstance(ig, list) or not all(_is_int(i) and -2 ** 63 <= i < 2 ** 63 for i in ig):
+        raise bad('ignore must be a list of integer zone ids, not %r' % (ig,))
+    if 'of' in v:
+        of = v['of']
+        if (not isinstance(of, list) or not of or
+                not all(isinstance(o, str) and o in ZONAL_OF for o in of) or
+                len(set(of)) != len(of)):
+            raise bad('of must be a non-empty list out of %s, not %r'
+                      % (', '.join('"%s"' % o for o in ZONAL_OF), of))
+        if 'change_maps' in of and 'change_maps' not in settings:
+            raise bad('of names change_maps, which this settings.json does not have')
+    # a table is named after its label rule or change map ('zonal-<name>.csv'): one name, one table
+    rules = [r.get('name') for r in settings.get('label_rules') or () if isinstance(r, dict)]
+    maps = [m.get('name') for m in settings.get('change_maps') or () if isinstance(m, dict)]
+    both = sorted(n for n in set(rules) & set(maps) if isinstance(n, str))
+    if both and set(v.get('of', ZONAL_OF)) == set(ZONAL_OF):
+        raise bad('the name %r is a label rule and a change map' % both[0])
+    return settings
+
+
+def zonal_stats_options(settings):
+    """settings['zonal_stats'] in full, {'zones', 'band', 'ignore' (sorted, distinct), 'of' (in
+    ZONAL_OF's order)} with the defaults filled in, or None if the key is absent. Without "of",
+    'of' is "labels" and, where the settings have change_maps, "change_maps"."""
+    if 'zonal_stats' not in check_zonal_stats(settings):
+        return None
+    v = settings['zonal_stats']
+    if isinstance(v, str):
+        v = {'zones': v}
+    of = v.get('of', [o for o in ZONAL_OF if o == 'labels' or 'change_maps' in settings])
+    return {'zones': v['zones'], 'band': v.get('band', 1),
+            'ignore': sorted(set(v.get('ignore', []))), 'of': [o for o in ZONAL_OF if o in of]}
+
+
 def _check_added(settings):
-    return check_change_maps(check_mmu(check_vertex_table(check_ftv_eqns(settings))))
+    return check_zonal_stats(
+        check_change_maps(check_mmu(check_vertex_table(check_ftv_eqns(settings)))))
 
 
 def load_settings(path_or_dict):
     """Read a settings.json (path, JSON text or dict) the way get_settings does (utils.py:241).
-    The keys the reference does not have, ftv_eqns, vertex_table, mmu and change_maps, are
-    validated here (check_ftv_eqns, check_vertex_table, check_mmu, check_change_maps)."""
+    The keys the reference does not have, ftv_eqns, vertex_table, mmu, change_maps and
+    zonal_stats, are validated here (check_ftv_eqns, check_vertex_table, check_mmu,
+    check_change_maps, check_zonal_stats)."""
     if isinstance(path_or_dict, dict):
         return _check_added(path_or_dict)
     if path_or_dict.lstrip().startswith('{'):

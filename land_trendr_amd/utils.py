@@ -23,7 +23,7 @@ from .settings import compile_params, load_settings, vertex_cap
 __all__ = ['parse_date', 'analyze', 'change_labeling', 'analysis_reducer',
            'analysis_reducer_batch', 'analyze_tile', 'index_tile', 'match_rules_gpu',
            'fit_to_vertices_tile', 'vertex_table', 'disturbances_from_vertices', 'sieve_labels',
-           'change_maps', 'label_counts']
+           'change_maps', 'label_counts', 'zonal_stats']
 
 
 def _raise_for_status(status, n_obs_valid):
@@ -98,6 +98,24 @@ def label_counts(matched, key, key_lo, n_bins, device=None):
     m = torch.from_numpy(np.ascontiguousarray(matched, np.uint8).reshape(-1)).to(eng.device)
     k = torch.from_numpy(np.ascontiguousarray(key, np.int32).reshape(-1)).to(eng.device)
     return eng.label_counts(m, k, key_lo, n_bins).cpu().numpy()
+
+
+def zonal_stats(matched, zone, key, key_lo, n_bins, n_zones, duration=None, value=None,
+                device=None):
+    """A label plane summed per zone and key on the GPU: matched [P] uint8, zone and key [P]
+    int32 and, optionally, duration [P] int32 and value [P] float64 -> int64 [n_zones + 1,
+    n_bins + 1, 4] (see Engine.zonal_stats). numpy arrays in, a numpy array out; device tensors
+    are taken and returned as they are."""
+    eng = get_engine(device)
+    if isinstance(matched, torch.Tensor):
+        return eng.zonal_stats(matched, zone, key, key_lo, n_bins, n_zones, duration, value)
+
+    def up(a, dt):
+        return None if a is None else torch.from_numpy(
+            np.ascontiguousarray(a, dt).reshape(-1)).to(eng.device)
+    return eng.zonal_stats(up(matched, np.uint8), up(zone, np.int32), up(key, np.int32), key_lo,
+                           n_bins, n_zones, up(duration, np.int32),
+                           up(value, np.float64)).cpu().numpy()
 
 
 def disturbances_from_vertices(table):

@@ -18,6 +18,13 @@ would, on cuda:0, and the script prints one JSON line:
                               [--sample {host,device}] [--shift N] [--mask PROB]
                               [--mask-eqn EQN | --qa-cloudmask] [--ftv EQN]
                               [--vertex-table [CAP]] [--mmu N] [--change-maps [N]]
+                              [--zonal [BLOCK]]
+
+--zonal [BLOCK]: a zone raster of BLOCK x BLOCK-pixel block zones (default 64; int32 ids from 1) is
+written beside the stack and settings.json gets zonal_stats, so the output step sums every rule's
+(and, with --change-maps, every map's) planes per zone and onset year on the GPU and writes the
+'tables/zonal-<name>.csv' files; the line reports the zones, the tables, their pixel totals, the
+CSV bytes and the pass's seconds (LocalJob.zonal_s, the zone raster's read and sampling included).
 
 --change-maps [N]: settings.json gets change_maps with the first N (default 8) of eight maps (loss /
 gain, several sorts and filters), so every tile's change maps are made on the GPU during the
@@ -271,6 +278,9 @@ def main():
     ap.add_argument('--change-maps', nargs='?', const=8, default=None, type=int, metavar='N',
                     help='settings.json change_maps: the first N of eight maps (the change maps '
                          "and their change/ rasters)")
+    ap.add_argument('--zonal', nargs='?', const=64, default=None, type=int, metavar='BLOCK',
+                    help='settings.json zonal_stats over BLOCK x BLOCK-pixel block zones (the '
+                         'per-zone, per-year tables)')
     ap.add_argument('--reuse', action='store_true',
                     help='use the stack an earlier --keep run left in --work (written with the '
                          'same size and format options) instead of writing it again: runs that '
@@ -319,6 +329,18 @@ def main():
             if not 1 <= a.change_maps <= len(CHANGE_MAPS):
                 ap.error('--change-maps takes 1 to %d' % len(CHANGE_MAPS))
             settings['change_maps'] = CHANGE_MAPS[:a.change_maps]
+        settings.pop('zonal_stats', None)
+        if a.zonal is not None:
+            if a.zonal < 1:
+                ap.error('--zonal takes a block size of at least 1')
+            from land_trendr_amd.raster import write_geotiff
+            nbw = (a.cols + a.zonal - 1) // a.zonal
+            zimg = (1 + (np.arange(a.rows, dtype=np.int32)[:, None] // a.zonal) * nbw +
+                    np.arange(a.cols, dtype=np.int32)[None, :] // a.zonal)
+            write_geotiff(os.path.join(a.work, 'bench', 'input', 'zones.tif'), zimg,
+                          geotransform=GT, nodata=0)
+            del zimg
+            settings['zonal_stats'] = 'zones.tif'
         with open(spath, 'w') as f:
             json.dump(settings, f)
         P = a.rows * a.cols
@@ -416,6 +438,14 @@ def main():
                 'device_bytes': sum(t.numel() * t.element_size()
                                     for t in j.change_planes.values()),
                 'rasters': len(cfiles), 'raster_bytes': sum(os.path.getsize(p) for p in cfiles)}
+        if a.zonal is not None:
+            zs = j.zonal_stats
+            res['zonal_stats'] = {
+                'block': a.zonal, 'pass_s': round(j.zonal_s, 4),
+                'zones': int(len(next(iter(zs.values()))['zone_ids'])), 'tables': sorted(zs),
+                'pixels': {k: int(v['pixels'].sum()) for k, v in zs.items()},
+                'outside': {k: int(v['pixels'][-1].sum()) for k, v in zs.items()},
+                'csv_bytes': sum(os.path.getsize(p) for p in j.zonal_files.values())}
         if a.diag:
             res['diag'] = diag(j)
         if a.check > 0:
